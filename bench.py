@@ -23,7 +23,17 @@ torch.distributed.run (before any GPU call) with one process per GPU; each rank 
 (weak scaling, no data-path collective except the RLC all-gather); value = all credentials /
 max-over-ranks time.
 
-cpu_baseline: the C restatement in oracle/ (test infrastructure, kind "port") timed on this host on a
+A plain run does what the headline needs and no more: synthetic data and verkey tables, warmup, the timed
+steps, the check of the last verdicts against construction, `--dump-outputs`, one JSON line.  `--full`
+adds every other leg after the timed region, as further keys of the same line: the per-kernel phase
+table and roofline, the committed rocprof / PMC summaries, the PCIe-inclusive rate, the library-default
+tables, single-call latency, the same-run SigG1 leg and the CPU baseline.
+
+`--dump-outputs DIR` writes what the last timed step handed its caller (verdicts; the aggregate mode's
+serialized points; the RLC decision) as DIR/<name>.npy in float32, one value per output byte; the inputs
+are seeded, so two builds run with the same arguments can be compared output for output.
+
+cpu_baseline (--full): the C restatement in oracle/ (test infrastructure, kind "port") timed on this host on a
 bounded sample of the same inputs (rank 0, N = 1 only): the threads this box grants (its CPU share)
 and one thread, with nproc and the CPU model.
 """
@@ -86,6 +96,29 @@ def table_config(ctx, q):
 def lib_info():
     import coconut
     return {"library": coconut.version(), "src_hash": coconut.source_hash()}
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(args, rank, world, arrays):
+    """--dump-outputs DIR: the arrays the last timed step handed its caller, as DIR/<name>.npy
+    (`<name>.rank<r>.npy` in a multi-rank job): float32 for byte arrays (one value per output byte),
+    float64 for wider integers, both exact.  All files of a job stay within DUMP_MAX_BYTES: a larger
+    array is cut to a fixed, seeded sample of its elements (in order)."""
+    if not args.dump_outputs:
+        return
+    import numpy as np
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    share = DUMP_MAX_BYTES // world // max(len(arrays), 1) - 1024  # bytes a file may take, header included
+    for name, a in arrays.items():
+        a = np.asarray(a).reshape(-1)
+        dt = np.float32 if a.dtype.itemsize == 1 else np.float64
+        keep = share // np.dtype(dt).itemsize
+        if a.size > keep:
+            a = a[np.sort(np.random.default_rng(0xD0).choice(a.size, size=keep, replace=False))]
+        np.save(os.path.join(args.dump_outputs, name + (f".rank{rank}" if world > 1 else "") + ".npy"),
+                a.astype(dt))
 
 
 def opcounts(key):
@@ -561,7 +594,8 @@ def bench_verify(args, mode, sub=None):
         step()
     torch.cuda.synchronize(dev)
     # phase timing (events + a host wait per call) only with one batch in flight: it would serialize them
-    timed_phases = K == 1
+    full = args.full
+    timed_phases = full and K == 1
     if timed_phases:
         ctx.timing(True)
     phase = np.zeros(3)
@@ -584,10 +618,12 @@ def bench_verify(args, mode, sub=None):
     for k in range(K):
         if rr[0] > k and not np.array_equal(d_vs[k].cpu().numpy(), batch["expect"]):
             raise SystemExit("verdicts disagree with construction — refusing to report a number")
+    if not sub:
+        dump_outputs(args, rank, world, {"verdicts": d_vs[(rr[0] - 1) % KK[0]].cpu().numpy()})
     ctx.set_concurrency(1)
     KK[0] = 1
     rr[0] = 0
-    if not timed_phases:  # the per-kernel table from a separate single-batch pass
+    if full and not timed_phases:  # the per-kernel table from a separate single-batch pass
         ctx.timing(True)
         for _ in range(min(args.steps, 5)):
             step()
@@ -610,7 +646,7 @@ def bench_verify(args, mode, sub=None):
     # PCIe-inclusive rate: the host-buffer entry point (H2D of the serialized batch + D2H of verdicts);
     # --no-pcie skips it (profiling runs: then every launch of the trace is a warmup or a timed step)
     pcie_rate = None
-    if not args.no_pcie:
+    if full and not args.no_pcie:
         v = coconut.verify_batch(ctx, n, q, batch["s1"], batch["s2"], batch["msgs"])  # sizes the host path's buffers
         assert np.array_equal(v, batch["expect"])
         reps = 3
@@ -630,29 +666,21 @@ def bench_verify(args, mode, sub=None):
         ok = all(np.array_equal(d_vs[k].cpu().numpy(), batch["expect"]) for k in range(min(K, rr[0])))
         ctx.set_concurrency(1)
         return ok
-    dflt = default_tables_leg(args, ctx, rebind_dflt, step, check_dflt, n, dev, dist)
-    dflt["batches_in_flight"] = K
-    dflt.update(table_config(ctx, q))
-    latency = latency_leg(ctx, d_s1, d_s2, d_m, q, batch["expect"], dev)
-    sigg1 = None
-    if mode == 0 and not args.no_sigg1:  # BASELINE config 2's own wording, same run, same K
+    dflt = latency = sigg1 = None
+    if full:
+        dflt = default_tables_leg(args, ctx, rebind_dflt, step, check_dflt, n, dev, dist)
+        dflt["batches_in_flight"] = K
+        dflt.update(table_config(ctx, q))
+        latency = latency_leg(ctx, d_s1, d_s2, d_m, q, batch["expect"], dev)
+    if full and mode == 0 and not args.no_sigg1:  # BASELINE config 2's own wording, same run, same K
         ctx.close()
         ctx = None
         del d_s1, d_s2, d_m, d_vs, d_v
         torch.cuda.empty_cache()
         sigg1 = bench_verify(args, 1, sub=(world, rank, local, dist))
     if rank == 0:
-        key = "verify_sigg2_q6_shared_vk" if mode == 0 else "verify_sigg1_q6_shared_vk"
-        counts = opcounts(key)
-        peak = peak_mad_per_s()
-        phase_ms = phase / max(args.steps, 1)
         sb = 192 if mode == 0 else 97
-        mname = "verify" if mode == 0 else "verify-g1"
-        kt = kernel_table(phase_ms, n, counts, 2 * sb + q * 48, peak,
-                          "k_prep_sigg2_pair" if mode == 0 else "k_prep_sigg1_pair", mname)
-        dom = max(kt, key=lambda k: kt[k]["ms"])
         ms_per_step = elapsed / args.steps * 1e3
-        total_mads = sum(counts.values()) * MADS_PER_M * n
         layout = "SigG2 (reference default: sigma in G2, verkey MSM in G1)" if mode == 0 else \
             "SigG1 (BASELINE config 2 wording: verkey MSM in G2, sigma in G1)"
         out = {
@@ -670,30 +698,43 @@ def bench_verify(args, mode, sub=None):
                        **opt_in, "verkey_tables": "opt-in width (bench); library default <= 4 GiB"},
             **lib_info(),
             "pairings_per_s": round(2 * value, 1),
-            "default_tables": dflt,
-            "latency": latency,
-            "roofline": {"bound": "valu-int", "kernel": dom, "achieved": kt[dom]["achieved_Tmad_s"],
-                         "peak": round(peak / 1e12, 3), "unit": "Tmad/s (v_mad_u64_u32, 32x32->64)",
-                         "frac": kt[dom]["frac"], "traffic": kt[dom].get("traffic_bytes"),
-                         "traffic_unit": "HBM-side bytes per launch (PMC, 2 x FETCH_SIZE + WRITE_SIZE)",
-                         "algorithmic_mads_per_credential": round(counts[dom] * MADS_PER_M),
-                         "opcount_fixture": "tests/fixtures/opcount.json (tools/opcount.py)",
-                         "whole_step_frac": round(total_mads / (ms_per_step * 1e-3) / peak, 4),
-                         "hbm_view_GBs": round(n * (2 * sb + q * 48 + 1) / (ms_per_step * 1e-3) / 1e9, 3),
-                         "hbm_peak_GBs": HBM_PEAK_GBS},
-            "kernels": kt,
-            "rocprof_kernels": kernel_pmc_report(mname),
-            "pcie_inclusive": {"value": round(pcie_rate, 1) if pcie_rate else None, "unit": "credentials/s",
-                               "note": "cc_verify_batch with host buffers, one call at a time (after one "
-                                       "untimed call that sizes its buffers): H2D of the serialized batch + D2H "
-                                       "of verdicts included (not `value`)"},
+            "verdicts_checked": "against construction (1/16 corrupted), every slot",
             "setup": {"verkey_tables_ms": round(vk_ms, 1), "verkey_table_bits": opt_in["verkey_table_bits"],
                       "synthetic_data_s": round(setup_s, 2)},
         }
-        if sigg1:
-            out["sigg1"] = sigg1
-        if not args.no_cpu_baseline and world == 1:
-            out["cpu_baseline"] = cpu_baseline_verify(batch, value)
+        if full:
+            key = "verify_sigg2_q6_shared_vk" if mode == 0 else "verify_sigg1_q6_shared_vk"
+            counts = opcounts(key)
+            peak = peak_mad_per_s()
+            phase_ms = phase / max(args.steps, 1)
+            mname = "verify" if mode == 0 else "verify-g1"
+            kt = kernel_table(phase_ms, n, counts, 2 * sb + q * 48, peak,
+                              "k_prep_sigg2_pair" if mode == 0 else "k_prep_sigg1_pair", mname)
+            dom = max(kt, key=lambda k: kt[k]["ms"])
+            total_mads = sum(counts.values()) * MADS_PER_M * n
+            out.update({
+                "default_tables": dflt,
+                "latency": latency,
+                "roofline": {"bound": "valu-int", "kernel": dom, "achieved": kt[dom]["achieved_Tmad_s"],
+                             "peak": round(peak / 1e12, 3), "unit": "Tmad/s (v_mad_u64_u32, 32x32->64)",
+                             "frac": kt[dom]["frac"], "traffic": kt[dom].get("traffic_bytes"),
+                             "traffic_unit": "HBM-side bytes per launch (PMC, 2 x FETCH_SIZE + WRITE_SIZE)",
+                             "algorithmic_mads_per_credential": round(counts[dom] * MADS_PER_M),
+                             "opcount_fixture": "tests/fixtures/opcount.json (tools/opcount.py)",
+                             "whole_step_frac": round(total_mads / (ms_per_step * 1e-3) / peak, 4),
+                             "hbm_view_GBs": round(n * (2 * sb + q * 48 + 1) / (ms_per_step * 1e-3) / 1e9, 3),
+                             "hbm_peak_GBs": HBM_PEAK_GBS},
+                "kernels": kt,
+                "rocprof_kernels": kernel_pmc_report(mname),
+                "pcie_inclusive": {"value": round(pcie_rate, 1) if pcie_rate else None, "unit": "credentials/s",
+                                   "note": "cc_verify_batch with host buffers, one call at a time (after one "
+                                           "untimed call that sizes its buffers): H2D of the serialized batch + D2H "
+                                           "of verdicts included (not `value`)"},
+            })
+            if sigg1:
+                out["sigg1"] = sigg1
+            if not args.no_cpu_baseline and world == 1:
+                out["cpu_baseline"] = cpu_baseline_verify(batch, value)
         print(json.dumps(out), flush=True)
     if dist:
         dist.destroy_process_group()
@@ -747,8 +788,9 @@ def bench_rlc(args):
         return ok
 
     # per-phase times come from a single-slot pass (the phase events of overlapping batches would overlap)
+    full = args.full
     phase = np.zeros(3)
-    if args.steps:
+    if full and args.steps:
         ctx.timing(True)
         assert run(min(args.steps, 5), phase)
         torch.cuda.synchronize(dev)
@@ -770,6 +812,7 @@ def bench_rlc(args):
     ctx.set_concurrency(1)
     if not ok:
         raise SystemExit("RLC rejected an all-valid batch — refusing to report a number")
+    dump_outputs(args, rank, world, {"accept": np.array([1.0 if ok else 0.0])})
     bad = d_s2.clone()
     if rank == 0:
         bad[:192] = d_s2[192:384]
@@ -783,7 +826,7 @@ def bench_rlc(args):
     # one NON-pipelined decision, as a single cc_verify_batch(..., rlc=1) call pays it: partial -> all-gather
     # -> finish -> accept on the host, nothing overlapped (the finish's one-wave kernels on the critical path)
     lat = []
-    for _ in range(3 if args.steps else 0):
+    for _ in range(3 if full and args.steps else 0):
         torch.cuda.synchronize(dev)
         if dist:
             dist.barrier()
@@ -800,12 +843,13 @@ def bench_rlc(args):
         ctx.set_concurrency(K)
         ok_dflt[0] &= run(k_steps, k_eng=K)
         ctx.set_concurrency(1)
-    dflt = default_tables_leg(args, ctx, lambda: ctx.set_verkey(batch["X"], batch["Y"]), None,
-                              lambda: ok_dflt[0], n, dev, dist, run_k=run_dflt)
-    dflt.update(table_config(ctx, q))
-    dflt["note"] += "; pipelined as the headline (finish of batch i under the partial of batch i + 1)"
+    dflt = None
+    if full:
+        dflt = default_tables_leg(args, ctx, lambda: ctx.set_verkey(batch["X"], batch["Y"]), None,
+                                  lambda: ok_dflt[0], n, dev, dist, run_k=run_dflt)
+        dflt.update(table_config(ctx, q))
+        dflt["note"] += "; pipelined as the headline (finish of batch i under the partial of batch i + 1)"
     if rank == 0:
-        phase_ms = phase / max(args.steps, 1)
         out = {
             "metric": "verified credentials/sec, RLC batch mode (msg_count=16)",
             "value": round(value, 1), "unit": "credentials/s", "n_gpus": world, "steps": args.steps,
@@ -818,6 +862,11 @@ def bench_rlc(args):
                        "batches_in_flight": K,
                        **opt_in, "verkey_tables": "opt-in width (bench); library default <= 4 GiB"},
             **lib_info(),
+            "us_per_credential": round(elapsed / args.steps / n * 1e6, 4),
+        }
+    if rank == 0 and full:
+        phase_ms = phase / max(args.steps, 1)
+        out.update({
             "single_call_ms": round(single_ms, 3) if single_ms else None,
             "single_call_note": "one non-pipelined RLC decision over the rank's credentials (partial -> "
                                 "all-gather -> finish -> host accept; best of 3): the latency a single "
@@ -825,8 +874,7 @@ def bench_rlc(args):
             "default_tables": dflt,
             "phase_ms": {"prep": round(phase_ms[0], 3), "miller": round(phase_ms[1], 3),
                          "reduce": round(phase_ms[2], 3)},
-            "us_per_credential": round(elapsed / args.steps / n * 1e6, 4),
-        }
+        })
         counts = opcounts("rlc_sigg2_q16")
         peak = peak_mad_per_s()
         kt = {}
@@ -848,6 +896,7 @@ def bench_rlc(args):
                                    "all-gather are outside the three phases but inside ms_per_step"}
         if not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline_verify(batch, value, "shared vk, per-credential verify")
+    if rank == 0:
         print(json.dumps(out), flush=True)
     if dist:
         dist.destroy_process_group()
@@ -870,6 +919,7 @@ def bench_stub(args):
     if dist:
         dist.barrier()
     el = _max_over_ranks(time.perf_counter() - t0, dist, "cpu")
+    dump_outputs(args, rank, world, {"state": a})
     if rank == 0:
         print(json.dumps({"metric": "stub (CPU skeleton check, not a measurement)", "value": None, "unit": None,
                           "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -891,6 +941,12 @@ def main():
     ap.add_argument("--iss-bits", type=int, default=None,
                     help="issuer table window width for the aggregate modes (cc_set_table_bits; 0 = the "
                          "library's <= 16 GiB choice; default: bench_modes.BENCH_ISS_BITS = 16)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other leg (per-kernel phases and roofline, PCIe-"
+                         "inclusive rate, library-default tables, latency, SigG1 leg, CPU baseline) and report "
+                         "them in the same line; a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned to its caller as DIR/<name>.npy (float32)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-pcie", action="store_true", help="skip the host-buffer (PCIe-inclusive) rate")
     ap.add_argument("--no-sigg1", action="store_true",

@@ -250,28 +250,22 @@ def bench_aggregate(args):
           and bytes(oX.cpu().numpy()) == b["want_X"] * n and bytes(oY.cpu().numpy()) == b["want_Y"] * n)
     if not ok:
         raise SystemExit("aggregation outputs disagree with construction — refusing to report a number")
+    from bench import dump_outputs
+    dump_outputs(args, rank, world, {"sigma1": o1.cpu().numpy(), "sigma2": o2.cpu().numpy(),
+                                     "verkey_X": oX.cpu().numpy(), "verkey_Y": oY.cpu().numpy()})
     value = n * world * args.steps / el
     opt_bits = ctx.table_bits()[1]
     from bench import default_tables_leg
+    full = args.full
 
     def agg_ok():
         return (bytes(o2.cpu().numpy()) == b["want_s2"] and bytes(oX.cpu().numpy()) == b["want_X"] * n
                 and bytes(oY.cpu().numpy()) == b["want_Y"] * n and not ctx.device_error(sh.value))
-    dflt = default_tables_leg(args, ctx, lambda: ctx.set_issuers(b["iss"], b["X"], b["Y"], b["q"]), step, agg_ok,
-                              n, dev, dist, table_kind="issuer")
-    dflt["issuer_table_gib"] = iss_table_gib(dflt["table_bits"], 100 * (q + 1), bool(sigm))
+    if full:
+        dflt = default_tables_leg(args, ctx, lambda: ctx.set_issuers(b["iss"], b["X"], b["Y"], b["q"]), step, agg_ok,
+                                  n, dev, dist, table_kind="issuer")
+        dflt["issuer_table_gib"] = iss_table_gib(dflt["table_bits"], 100 * (q + 1), bool(sigm))
     if rank == 0:
-        peak = peak_mad_per_s()
-        # phases: Lagrange, Signature::aggregate (Verkey::aggregate runs concurrently on the side stream),
-        # the rest of Verkey::aggregate after it; the roofline counts both MSMs' mads over their common span
-        sig_ms, vk_ms = phase[1], phase[2]
-        msm_ms = sig_ms + vk_ms
-        # the op-count fixture covers SigG2; SigG1 lines report times only
-        counts = opcounts("aggregate_sigg1_t67" if sigm else "aggregate_sigg2_t67")
-        ach = (counts["straus_sigma2"] + counts["fixed_verkey"]) * MADS_PER_M * n / (msm_ms * 1e-3)
-        dom = "signature_msm+verkey_msm (concurrent)"
-        from bench import kernel_pmc_report
-        rk = kernel_pmc_report("aggregate-g1" if sigm else "aggregate")
         out = {
             "metric": "aggregated credentials/sec (Signature::aggregate + Verkey::aggregate, t=67 of n=100)",
             "value": round(value, 1), "unit": "credentials/s", "n_gpus": world, "steps": args.steps,
@@ -285,6 +279,21 @@ def bench_aggregate(args):
                        "parallelism": f"shard-by-credential x{world}", "issuer_table_bits": opt_bits,
                        "issuer_table_gib": iss_table_gib(opt_bits, 100 * (q + 1), bool(sigm))},
             **__import__("bench").lib_info(),
+            "setup": {"issuer_tables_ms": round(iss_ms, 1), "synthetic_data_s": round(gen_s, 2)},
+        }
+    if rank == 0 and full:
+        peak = peak_mad_per_s()
+        # phases: Lagrange, Signature::aggregate (Verkey::aggregate runs concurrently on the side stream),
+        # the rest of Verkey::aggregate after it; the roofline counts both MSMs' mads over their common span
+        sig_ms, vk_ms = phase[1], phase[2]
+        msm_ms = sig_ms + vk_ms
+        # the op-count fixture covers SigG2; SigG1 lines report times only
+        counts = opcounts("aggregate_sigg1_t67" if sigm else "aggregate_sigg2_t67")
+        ach = (counts["straus_sigma2"] + counts["fixed_verkey"]) * MADS_PER_M * n / (msm_ms * 1e-3)
+        dom = "signature_msm+verkey_msm (concurrent)"
+        from bench import kernel_pmc_report
+        rk = kernel_pmc_report("aggregate-g1" if sigm else "aggregate")
+        out.update({
             "default_tables": dflt,
             "roofline": {"bound": "valu-int", "kernel": dom, "achieved": round(ach / 1e12, 3),
                          "peak": round(peak / 1e12, 3), "unit": "Tmad/s (v_mad_u64_u32, 32x32->64)",
@@ -296,10 +305,10 @@ def bench_aggregate(args):
             "kernels": {"lagrange_ms": round(phase[0], 3), "msm_ms": round(msm_ms, 3),
                         "signature_msm_ms": round(sig_ms, 3), "verkey_msm_tail_ms": round(vk_ms, 3)},
             "rocprof_kernels": rk,
-            "setup": {"issuer_tables_ms": round(iss_ms, 1), "synthetic_data_s": round(gen_s, 2)},
-        }
+        })
         if not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_aggregate(b, value)
+    if rank == 0:
         print(json.dumps(out), flush=True)
     if dist:
         dist.destroy_process_group()
@@ -376,12 +385,15 @@ def bench_pok(args):
         if st:
             raise RuntimeError(f"cc_pok_verify_batch_device: {lib.cc_status_str(st).decode()}")
 
-    el, phase_ms = _timed(args, step, dev, dist, ctx, phases=K == 1)
+    full = args.full
+    el, phase_ms = _timed(args, step, dev, dist, ctx, phases=full and K == 1)
     for k in range(K):
         if rr[0] > k and not np.array_equal(d_vs[k].cpu().numpy(), b["expect"]):
             raise SystemExit("PoK verdicts disagree with construction — refusing to report a number")
+    from bench import dump_outputs
+    dump_outputs(args, rank, world, {"verdicts": d_vs[(rr[0] - 1) % K].cpu().numpy()})
     K0 = K
-    if K > 1:  # the per-kernel table from a separate single-batch pass
+    if full and K > 1:  # the per-kernel table from a separate single-batch pass
         ctx.set_concurrency(1)
         K = 1
         rr[0] = 0
@@ -407,9 +419,10 @@ def bench_pok(args):
         ok = all(np.array_equal(d_vs[k].cpu().numpy(), b["expect"]) for k in range(min(K0, rr[0])))
         ctx.set_concurrency(1)
         return ok
-    dflt = default_tables_leg(args, ctx, rebind_dflt, step, check_dflt, n, dev, dist, unit="proofs/s")
-    dflt["batches_in_flight"] = K0
-    dflt.update(table_config(ctx, q))
+    if full:
+        dflt = default_tables_leg(args, ctx, rebind_dflt, step, check_dflt, n, dev, dist, unit="proofs/s")
+        dflt["batches_in_flight"] = K0
+        dflt.update(table_config(ctx, q))
     from bench import latency_of
 
     def pok_launch(nn, d_vv, sh):  # the first nn proofs (proof-major inputs)
@@ -417,14 +430,9 @@ def bench_pok(args):
                                             P("chal"), ridx, P("rev"), ctypes.c_void_p(d_vv.data_ptr()), None, sh)
         if st:
             raise RuntimeError(f"cc_pok_verify_batch_device: {lib.cc_status_str(st).decode()}")
-    latency = latency_of(ctx, pok_launch, b["expect"], dev, what="proofs")
+    if full:
+        latency = latency_of(ctx, pok_launch, b["expect"], dev, what="proofs")
     if rank == 0:
-        from bench import kernel_table, cpu_info, kernel_pmc_report
-        peak = peak_mad_per_s()
-        counts = opcounts("pok_sigg1_q32_r8" if sigm else "pok_sigg2_q32_r8")
-        kt = kernel_table(phase_ms, n, counts, 2 * 192 + 2 * 97 + (nresp + 1 + r) * 48, peak,
-                          "k_prep_pok_g1pl" if sigm else "k_prep_pok_split", "pok-g1" if sigm else "pok")
-        dom = max(kt, key=lambda k: kt[k]["ms"])
         out = {
             "metric": "verified PoK-of-signature proofs/sec (msg_count=32, 8 revealed)",
             "value": round(value, 1), "unit": "proofs/s", "n_gpus": world, "steps": args.steps,
@@ -437,6 +445,16 @@ def bench_pok(args):
                        "batches_in_flight": max(1, getattr(args, "inflight", 1)),
                        "verkey_tables": "opt-in width (bench); library default <= 4 GiB"},
             **__import__("bench").lib_info(),
+            "setup": {"synthetic_data_s": round(gen_s, 2), "verkey_table_bits": opt_in["verkey_table_bits"]},
+        }
+    if rank == 0 and full:
+        from bench import kernel_table, cpu_info, kernel_pmc_report
+        peak = peak_mad_per_s()
+        counts = opcounts("pok_sigg1_q32_r8" if sigm else "pok_sigg2_q32_r8")
+        kt = kernel_table(phase_ms, n, counts, 2 * 192 + 2 * 97 + (nresp + 1 + r) * 48, peak,
+                          "k_prep_pok_g1pl" if sigm else "k_prep_pok_split", "pok-g1" if sigm else "pok")
+        dom = max(kt, key=lambda k: kt[k]["ms"])
+        out.update({
             "default_tables": dflt,
             "latency": latency,
             "roofline": {"bound": "valu-int", "kernel": dom, "achieved": kt[dom]["achieved_Tmad_s"],
@@ -445,8 +463,7 @@ def bench_pok(args):
                          "traffic_unit": "HBM-side bytes per launch (PMC, 2 x FETCH_SIZE + WRITE_SIZE)"},
             "kernels": kt,
             "rocprof_kernels": kernel_pmc_report("pok-g1" if sigm else "pok"),
-            "setup": {"synthetic_data_s": round(gen_s, 2), "verkey_table_bits": opt_in["verkey_table_bits"]},
-        }
+        })
         if not args.no_cpu_baseline and world == 1:
             from bench import _oracle, cpu_pool_rate, cpu_report, host_threads
             oc = _oracle()
@@ -467,6 +484,7 @@ def bench_pok(args):
             st = cpu_pool_rate(one, n, 1, 2.5)
             out["cpu_baseline"] = cpu_report(value, "proofs/s", "oc_pok_verify per proof", mt, st, thr,
                                              all(mt[3]) and all(st[3]))
+    if rank == 0:
         print(json.dumps(out), flush=True)
     if dist:
         dist.destroy_process_group()
@@ -509,11 +527,14 @@ def bench_pervk(args):
         if st:
             raise RuntimeError(f"cc_verify_batch_pervk_device: {lib.cc_status_str(st).decode()}")
 
-    el, phase_ms = _timed(args, step, dev, dist, ctx, phases=K == 1)
+    full = args.full
+    el, phase_ms = _timed(args, step, dev, dist, ctx, phases=full and K == 1)
     for k in range(K):
         if rr[0] > k and not np.array_equal(d_vs[k].cpu().numpy(), b["expect"]):
             raise SystemExit("per-verkey verdicts disagree with construction — refusing to report a number")
-    if K > 1:  # the per-kernel table from a separate single-batch pass
+    from bench import dump_outputs
+    dump_outputs(args, rank, world, {"verdicts": d_vs[(rr[0] - 1) % K].cpu().numpy()})
+    if full and K > 1:  # the per-kernel table from a separate single-batch pass
         ctx.set_concurrency(1)
         K = 1
         rr[0] = 0
@@ -531,16 +552,9 @@ def bench_pervk(args):
         st = lib.cc_verify_batch_pervk_device(ctx.h, nn, q, *P, ctypes.c_void_p(d_vv.data_ptr()), None, sh)
         if st:
             raise RuntimeError(f"cc_verify_batch_pervk_device: {lib.cc_status_str(st).decode()}")
-    latency = latency_of(ctx, pervk_launch, b["expect"], dev)
+    if full:
+        latency = latency_of(ctx, pervk_launch, b["expect"], dev)
     if rank == 0:
-        key = "verify_sigg2_q6_pervk" if mode == 0 else "verify_sigg1_q6_pervk"
-        counts = opcounts(key)
-        peak = peak_mad_per_s()
-        sb, ob = (192, 97) if mode == 0 else (97, 192)
-        kt = kernel_table(phase_ms, n, counts, 2 * sb + q * 48 + (q + 1) * ob, peak,
-                          "k_prep_sigg2_var" if mode == 0 else "k_prep_sigg1_var", args.mode)
-        dom = max(kt, key=lambda k: kt[k]["ms"])
-        total = sum(counts.values()) * MADS_PER_M * n
         out = {
             "metric": "verified credentials/sec (msg_count=6), one verkey per credential" + ("" if mode == 0 else " [SigG1]"),
             "value": round(value, 1), "unit": "credentials/s", "n_gpus": world, "steps": args.steps,
@@ -554,6 +568,18 @@ def bench_pervk(args):
                        "credentials_per_gpu": n, "msg_count": q, "parallelism": f"shard-by-credential x{world}",
                        "batches_in_flight": max(1, getattr(args, "inflight", 1))},
             **lib_info(),
+            "setup": {"synthetic_data_s": round(gen_s, 2)},
+        }
+    if rank == 0 and full:
+        key = "verify_sigg2_q6_pervk" if mode == 0 else "verify_sigg1_q6_pervk"
+        counts = opcounts(key)
+        peak = peak_mad_per_s()
+        sb, ob = (192, 97) if mode == 0 else (97, 192)
+        kt = kernel_table(phase_ms, n, counts, 2 * sb + q * 48 + (q + 1) * ob, peak,
+                          "k_prep_sigg2_var" if mode == 0 else "k_prep_sigg1_var", args.mode)
+        dom = max(kt, key=lambda k: kt[k]["ms"])
+        total = sum(counts.values()) * MADS_PER_M * n
+        out.update({
             "roofline": {"bound": "valu-int", "kernel": dom, "achieved": kt[dom]["achieved_Tmad_s"],
                          "peak": round(peak / 1e12, 3), "unit": "Tmad/s (v_mad_u64_u32, 32x32->64)",
                          "frac": kt[dom]["frac"], "traffic": kt[dom].get("traffic_bytes"),
@@ -565,12 +591,12 @@ def bench_pervk(args):
             "prep_over_miller": round(kt["prep"]["ms"] / kt["miller"]["ms"], 3) if kt["miller"]["ms"] else None,
             "latency": latency,
             "rocprof_kernels": __import__("bench").kernel_pmc_report(args.mode),
-            "setup": {"synthetic_data_s": round(gen_s, 2)},
-        }
+        })
         if not args.no_cpu_baseline and world == 1:
             cb = dict(mode=mode, q=q, n=n, s1=b["s1"], s2=b["s2"], msgs=b["msgs"], X=b["X"], Y=b["Y"],
                       g_tilde=b["g_tilde"], expect=b["expect"], per_vk=True)
             out["cpu_baseline"] = cpu_baseline_verify(cb, value, "per-credential verkeys")
+    if rank == 0:
         print(json.dumps(out), flush=True)
     if dist:
         dist.destroy_process_group()

@@ -20,7 +20,7 @@ pytestmark = pytest.mark.gpu
 def _bench(*args):
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "2",
-           "--warmup", "1", "--no-cpu-baseline", "--no-pcie", "--vk-bits", "16", *args]
+           "--warmup", "1", "--full", "--no-cpu-baseline", "--no-pcie", "--vk-bits", "16", *args]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

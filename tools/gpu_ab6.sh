@@ -36,7 +36,7 @@ for m in ${MODES:-verify}; do
         fi
         [ -f "$lib" ] || continue
         f="$OUT/${m}_a${a}_${v}.$k.json"
-        env "${penv[@]}" COCONUT_HIP_LIB=$lib timeout -k 10 400 python -u bench.py --mode $m --steps ${STEPS:-20} --warmup 3 --no-cpu-baseline --no-pcie --no-sigg1 $args > "$f" 2> "${f%.json}.err" || { tail -20 "${f%.json}.err"; exit 1; }
+        env "${penv[@]}" COCONUT_HIP_LIB=$lib timeout -k 10 400 python -u bench.py --full --mode $m --steps ${STEPS:-20} --warmup 3 --no-cpu-baseline --no-pcie --no-sigg1 $args > "$f" 2> "${f%.json}.err" || { tail -20 "${f%.json}.err"; exit 1; }
         python3 -c "import json,sys;d=json.load(open('$f'));k=d.get('kernels',{});print('[ab] $m [$args] $v $k', d['value'], d['ms_per_step'], {x:(y.get('ms') if isinstance(y, dict) else y) for x,y in k.items()})"
       done
     done
@@ -44,7 +44,7 @@ for m in ${MODES:-verify}; do
   if [ "${PROF:-0}" = 1 ]; then
     P=$OUT/prof_$m
     mkdir -p "$P"
-    (cd /tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats -d "$P/prof" -o bench --output-format csv -- python3 "$R/bench.py" --mode $m --steps 20 --warmup 2 --no-cpu-baseline --no-pcie --no-sigg1 --inflight 1 > "$P/prof_bench.json" 2> "$P/prof.err") || { echo "rocprof failed"; exit 1; }
+    (cd /tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats -d "$P/prof" -o bench --output-format csv -- python3 "$R/bench.py" --full --mode $m --steps 20 --warmup 2 --no-cpu-baseline --no-pcie --no-sigg1 --inflight 1 > "$P/prof_bench.json" 2> "$P/prof.err") || { echo "rocprof failed"; exit 1; }
     PMC_OUT="$P/pmc" BENCH_ARGS="--mode $m" bash tools/pmc_round.sh > "$P/pmc.log" 2>&1 || { echo "pmc failed"; exit 1; }
     python3 tools/pmc_summary.py "$P/pmc" "$P/pmc_summary.json" > "$P/pmc_summary.log" 2>&1
     echo "[ab] prof $m done"

@@ -18,7 +18,7 @@ for r in $(seq 1 "$REPS"); do
     lib=$(pwd)/coconut-rust_amd/libcoconut_hip.so
     [ $v = prev ] && lib=$(pwd)/coconut-rust_amd/libcoconut_hip_prev.so
     echo "[abalt] $MODE $v $r"
-    COCONUT_HIP_LIB=$lib timeout -k 10 300 python -u bench.py --mode "$MODE" --steps 8 --warmup 2 --no-cpu-baseline ${BENCH_ARGS:-} > "$OUT/${MODE}_${v}_$r.json" 2> "$OUT/${MODE}_${v}_$r.err" || exit 1
+    COCONUT_HIP_LIB=$lib timeout -k 10 300 python -u bench.py --full --mode "$MODE" --steps 8 --warmup 2 --no-cpu-baseline ${BENCH_ARGS:-} > "$OUT/${MODE}_${v}_$r.json" 2> "$OUT/${MODE}_${v}_$r.err" || exit 1
     python3 -c "import json,sys; d=json.load(open(sys.argv[1])); print(d['value'], d.get('phase_ms'))" "$OUT/${MODE}_${v}_$r.json"
   done
 done

@@ -12,7 +12,7 @@ for k in 1 2; do
     lib=$(pwd)/coconut-rust_amd/libcoconut_hip.so
     [ $v = prev ] && lib=$(pwd)/coconut-rust_amd/libcoconut_hip_prev.so
     echo "[ab] $v $k"
-    COCONUT_HIP_LIB=$lib timeout -k 10 300 python -u bench.py --mode $MODE --steps 10 --warmup 2 --no-cpu-baseline > "$OUT/${MODE}_$v.$k.json" 2>&1 || exit 1
+    COCONUT_HIP_LIB=$lib timeout -k 10 300 python -u bench.py --full --mode $MODE --steps 10 --warmup 2 --no-cpu-baseline > "$OUT/${MODE}_$v.$k.json" 2>&1 || exit 1
   done
 done
 echo "[ab] done"

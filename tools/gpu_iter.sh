@@ -18,7 +18,7 @@ for k in 1 2; do
     [ $v = prev ] && lib=$(pwd)/coconut-rust_amd/libcoconut_hip_prev.so
     [ -f "$lib" ] || continue
     echo "[iter] bench $v $k"
-    COCONUT_HIP_LIB=$lib timeout -k 10 300 python -u bench.py --mode $MODE --steps 10 --warmup 2 --no-cpu-baseline > "$OUT/${MODE}_$v.$k.json" 2> "$OUT/${MODE}_$v.$k.err" || exit 1
+    COCONUT_HIP_LIB=$lib timeout -k 10 300 python -u bench.py --full --mode $MODE --steps 10 --warmup 2 --no-cpu-baseline > "$OUT/${MODE}_$v.$k.json" 2> "$OUT/${MODE}_$v.$k.err" || exit 1
   done
 done
 if [ -f coconut-rust_amd/libcoconut_hip_prof.so ]; then
@@ -34,7 +34,7 @@ if [ -n "${PMC_GROUPS:-}" ]; then
   for grp in "${GRPS[@]}"; do
     i=$((i+1))
     echo "[iter] pmc $i: $grp"
-    (cd /tmp && timeout -k 10 120 rocprofv3 --kernel-trace --pmc $grp -d "$OLDPWD/$OUT/pmc$i" -o pmc --output-format csv -- python3 "$OLDPWD/bench.py" --mode $MODE --steps 1 --warmup 0 --no-cpu-baseline --no-pcie > "$OLDPWD/$OUT/pmc$i.log" 2>&1) || exit 1
+    (cd /tmp && timeout -k 10 120 rocprofv3 --kernel-trace --pmc $grp -d "$OLDPWD/$OUT/pmc$i" -o pmc --output-format csv -- python3 "$OLDPWD/bench.py" --full --mode $MODE --steps 1 --warmup 0 --no-cpu-baseline --no-pcie > "$OLDPWD/$OUT/pmc$i.log" 2>&1) || exit 1
   done
 fi
 echo "[iter] pmc done"

@@ -11,7 +11,7 @@ for m in $MODES; do
       lib=$(pwd)/coconut-rust_amd/libcoconut_hip.so
       [ $v = prev ] && lib=$(pwd)/coconut-rust_amd/libcoconut_hip_prev.so
       echo "[ab] $m $v $k"
-      COCONUT_HIP_LIB=$lib timeout -k 10 300 python -u bench.py --mode $m --steps 10 --warmup 2 --no-cpu-baseline --no-pcie > "$OUT/${m}_$v.$k.json" 2> "$OUT/${m}_$v.$k.err" || { tail -5 "$OUT/${m}_$v.$k.err"; exit 1; }
+      COCONUT_HIP_LIB=$lib timeout -k 10 300 python -u bench.py --full --mode $m --steps 10 --warmup 2 --no-cpu-baseline --no-pcie > "$OUT/${m}_$v.$k.json" 2> "$OUT/${m}_$v.$k.err" || { tail -5 "$OUT/${m}_$v.$k.err"; exit 1; }
     done
   done
 done

@@ -5,7 +5,7 @@ set -o pipefail
 OUT=gpurun_out/${1:-r05l}
 mkdir -p $OUT
 run() {  # name, args
-  timeout -k 10 400 python -X faulthandler bench.py $2 > $OUT/$1.json 2> $OUT/$1.err || { tail -5 $OUT/$1.err; exit 1; }
+  timeout -k 10 400 python -X faulthandler bench.py --full $2 > $OUT/$1.json 2> $OUT/$1.err || { tail -5 $OUT/$1.err; exit 1; }
   python3 -c "import json; d=json.loads(open('$OUT/$1.json').read().strip().splitlines()[-1]); print('$1', d['value'], d['ms_per_step'], {k: v['ms'] for k, v in d.get('kernels', {}).items()}, json.dumps(d.get('latency')))"
 }
 run verify "--steps 20 --warmup 3 --no-cpu-baseline --no-pcie"

@@ -5,7 +5,7 @@ set -o pipefail
 OUT=gpurun_out/${1:-r05d}
 mkdir -p $OUT
 run() {  # name, args
-  timeout -k 10 400 python -X faulthandler bench.py $2 > $OUT/$1.json 2> $OUT/$1.err || { tail -5 $OUT/$1.err; exit 1; }
+  timeout -k 10 400 python -X faulthandler bench.py --full $2 > $OUT/$1.json 2> $OUT/$1.err || { tail -5 $OUT/$1.err; exit 1; }
   python3 -c "import json; d=json.loads(open('$OUT/$1.json').read().strip().splitlines()[-1]); print('$1', d['value'], d['ms_per_step'], d['config'].get('batches_in_flight'), (d.get('default_tables') or {}).get('value'), d.get('single_call_ms'))"
 }
 timeout -k 10 300 python -u -X faulthandler -m pytest tests/test_gpu_parity.py tests/test_gpu_rlc.py -m gpu -q --timeout 200 --timeout-method thread -p no:cacheprovider -k "concurrent or slots" > $OUT/pytest.log 2>&1 || { tail -30 $OUT/pytest.log; exit 1; }

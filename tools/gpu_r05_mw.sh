@@ -12,5 +12,5 @@ python3 -c "
 import json
 for l in open('$OUT/latency.jsonl'):
     d = json.loads(l); print(d['mode'], d['n'], d['ok'], d['device_ms_median'], d['phase_ms'])"
-timeout -k 10 400 python -X faulthandler bench.py --mode rlc --steps 10 --warmup 2 --no-cpu-baseline > $OUT/rlc.json 2> $OUT/rlc.err || { tail -5 $OUT/rlc.err; exit 1; }
+timeout -k 10 400 python -X faulthandler bench.py --full --mode rlc --steps 10 --warmup 2 --no-cpu-baseline > $OUT/rlc.json 2> $OUT/rlc.err || { tail -5 $OUT/rlc.err; exit 1; }
 python3 -c "import json; d=json.loads(open('$OUT/rlc.json').read().strip().splitlines()[-1]); print('rlc', d['value'], d['ms_per_step'], d.get('single_call_ms'))"

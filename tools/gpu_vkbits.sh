@@ -9,7 +9,7 @@ mkdir -p "$OUT"
 for b in $BITS; do
   for m in verify rlc pok; do
     echo "[vkbits] $m $b"
-    timeout -k 10 300 python -u bench.py --mode $m --steps 5 --warmup 1 --no-cpu-baseline --no-pcie --vk-bits $b > "$OUT/${m}_$b.json" 2> "$OUT/${m}_$b.err"
+    timeout -k 10 300 python -u bench.py --full --mode $m --steps 5 --warmup 1 --no-cpu-baseline --no-pcie --vk-bits $b > "$OUT/${m}_$b.json" 2> "$OUT/${m}_$b.err"
   done
 done
 echo "[vkbits] done"
