@@ -115,7 +115,7 @@ def buf(b):
 def need(b, nbytes: int, what: str):
     """The byte count the C ABI will read from `b` (it trusts the caller's counts): a shorter buffer
     is CC_ERR_DECODE here instead of a read past its end there."""
-    if nbytes > 0 and (b is None or len(b) < nbytes):
+    got = 0 if b is None else memoryview(b).nbytes  # bytes, not len(): a 2-D or wide-dtype array counts in full
+    if nbytes > 0 and got < nbytes:
         from .errors import CoconutError
-        got = 0 if b is None else len(b)
         raise CoconutError(-4, f"{what}: {got} bytes, the call reads {nbytes}")

@@ -13,7 +13,7 @@
 // No HIP types here: the device is a policy class.  capi.cpp instantiates it over hipMalloc'd buffers
 // and hipEvent_t (HipDev); tests/host/test_slots.cpp over a simulated device timeline that flags a
 // buffer reallocated while a queued operation still reads it, built with -fsanitize=address,undefined
-// (tests/test_host_slots.py, `pytest -m "not gpu"`).
+// (tests/test_sanitizers.py, `pytest -m "not gpu"`).
 #pragma once
 #include <stddef.h>
 

@@ -140,3 +140,24 @@ def test_python_mirror_checks_buffer_lengths(ctx):
     with pytest.raises(CoconutError):
         pok_verify_batch(ctx, 2, q, [], q + 1, s, s, bytes(2 * 97), bytes(2 * 97), bytes(2 * (q + 1) * 48 - 48),
                          bytes(2 * 48), b"")
+    # the count is in bytes, whatever the array's shape or dtype: (n, 192) uint8 rows and uint64 words
+    # of exactly the size the call reads pass the check (and verify to 0: all-zero encodings) ...
+    n = 4
+    s2d = np.zeros((n, sb), dtype=np.uint8)
+    m2d = np.zeros((n * q, 48), dtype=np.uint8)
+    v = coconut.verify_batch(ctx, n, q, s2d, s2d, m2d)
+    assert len(v) == n and not v.any()
+    s64 = np.zeros(n * sb // 8, dtype=np.uint64)
+    m64 = np.zeros(n * q * 48 // 8, dtype=np.uint64)
+    v = coconut.verify_batch(ctx, n, q, s64, s64, m64)
+    assert len(v) == n and not v.any()
+    # ... and one byte short still fails, in either shape
+    with pytest.raises(CoconutError) as e:
+        coconut.verify_batch(ctx, n, q, s2d, s2d, np.zeros(n * q * 48 - 1, dtype=np.uint8))
+    assert e.value.kind == CoconutErrorKind.Decode
+    with pytest.raises(CoconutError) as e:
+        coconut.verify_batch(ctx, n, q, s2d[:, :sb - 1], s2d, m2d)  # (n, 191): n bytes short
+    assert e.value.kind == CoconutErrorKind.Decode
+    with pytest.raises(CoconutError) as e:
+        coconut.verify_batch(ctx, n, q, s64[:-1], s64, m64)  # one uint64 word short
+    assert e.value.kind == CoconutErrorKind.Decode
