@@ -165,7 +165,8 @@ __global__ __launch_bounds__(64) void k_lagrange(size_t n, size_t len, size_t t,
 // trick over all 8t entries), then 65 windows x (4 doublings + t mixed additions).  For t = 67 in G2
 // that is ~147k Fp multiplications per task against ~253k for the bitwise double-and-add it
 // replaces.  Identity bases (AMCL decodes an off-curve point to infinity) and identity multiples of
-// small-order points are flagged and skipped, so every input gives the reference's group element.
+// small-order points are flagged and skipped, so every input gives the reference's group element
+// (tests/test_gpu_straus_edges.py).
 // Scratch per task (AoS, contiguous): 8t Jacobian entries (3*FS*12 words, affine x,y written back in
 // place, word 2*FS*12 = infinity flag), 8t prefix products (FS*12 words), 65t digit bytes.
 template <class F>

@@ -3,7 +3,9 @@
 // per base the multiples 1P..8P built in Jacobian form and batch-normalised to affine with ONE inversion
 // per lane (Montgomery's trick), then 65 windows x (4 doublings + one mixed addition per base).
 // Identity bases (AMCL decodes an off-curve point to infinity) and identity multiples of small-order
-// points are flagged and skipped, so every input gives the reference's group element.
+// points are flagged and skipped, so every input gives the reference's group element
+// (tests/test_gpu_straus_edges.py: edge digits, related bases, identity, off-curve and order-3 bases in
+// every layout, byte-exact against the oracle; tests/straus_edges.py models which branch each reaches).
 #pragma once
 #include "codec.h"
 #include "curve_lz.h"

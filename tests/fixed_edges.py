@@ -110,29 +110,30 @@ def edge_scalars(wbits):
 
 # ---------------------------------------------------------------- the model: branches of the additions
 class Chain:
-    """An accumulator and the branch each mixed addition into it takes (points as multiples mod r)."""
+    """An accumulator and the branch each mixed addition into it takes (points as multiples mod r; `mod`:
+    the order of another cyclic group the points are counted in, tests/straus_edges.py)."""
 
-    def __init__(self, start=0):
-        self.acc, self.seen, self.log = start % R, start % R != 0, []
+    def __init__(self, start=0, mod=R):
+        self.mod, self.acc, self.seen, self.log = mod, start % mod, start % mod != 0, []
 
     def add(self, e):
-        e %= R
+        e %= self.mod
         assert e, "a table entry is never the identity"
         if self.acc == 0:
             b = "from-identity" if self.seen else "fresh"
         elif self.acc == e:
             b = "doubling"
-        elif (self.acc + e) % R == 0:
+        elif (self.acc + e) % self.mod == 0:
             b = "to-identity"
         else:
             b = "general"
         self.seen = True
         self.log.append(b)
-        self.acc = (self.acc + e) % R
+        self.acc = (self.acc + e) % self.mod
         return b
 
 
-def join(p, q, log):
+def join(p, q, log, mod=R):
     """A full addition p + q (the exceptional cases in the order jg_add / jac_add test them)."""
     if p == 0:
         b = "left-identity"
@@ -140,12 +141,12 @@ def join(p, q, log):
         b = "right-identity"
     elif p == q:
         b = "doubling"
-    elif (p + q) % R == 0:
+    elif (p + q) % mod == 0:
         b = "to-identity"
     else:
         b = "general"
     log.append(b)
-    return (p + q) % R
+    return (p + q) % mod
 
 
 def butterfly_low_first(vals, log):
