@@ -190,3 +190,50 @@ class DeviceEngine:
                     "cc_verify_batch_device")
         self._leave()
         return self.verdicts.cpu().numpy()
+
+
+class PokDeviceEngine(DeviceEngine):
+    """One rank's slice of a PoKOfSignatureProof::verify batch, resident in HBM as torch tensors: the
+    interface of DeviceEngine (partial / finish / finish_async / per_credential), so rlc_accept,
+    verify_sharded and gather_partials serve PoK batches unchanged.  The partial is
+    ``cc_pok_rlc_partial_device`` (finished by ``cc_rlc_finish_device``, like a signature shard's), the
+    per-proof path ``cc_pok_verify_batch_device``.  revealed_idx is a host sequence shared by the batch."""
+
+    def __init__(self, ctx, n: int, q: int, revealed_idx, d_s1, d_s2, d_J, d_T, d_responses, d_chal,
+                 d_revealed_msgs, base_index: int = 0, seed: Optional[bytes] = None, stream=None):
+        super().__init__(ctx, n, q, d_s1, d_s2, None, base_index=base_index, seed=seed, stream=stream)
+        self.r = len(revealed_idx)
+        self.nresp = q - self.r + 1
+        self.idx = (np.ascontiguousarray(np.asarray(revealed_idx, dtype=np.uint64)) if self.r
+                    else np.zeros(1, np.uint64))
+        self.d_J, self.d_T, self.d_responses, self.d_chal = d_J, d_T, d_responses, d_chal
+        self.d_revealed_msgs = d_revealed_msgs
+
+    def _proof_args(self):
+        p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+        return (p(self.d_s1), p(self.d_s2), p(self.d_J), p(self.d_T), p(self.d_responses), p(self.d_chal),
+                ctypes.c_void_p(self.idx.ctypes.data), p(self.d_revealed_msgs))
+
+    def partial(self):
+        seed = self.seed if self.seed is not None else os.urandom(32)
+        self._slot ^= 1
+        self.part = self._parts[self._slot]
+        self._enter()
+        if self._slot_ev[self._slot] is not None:  # a finish_async still reading this slot
+            self.stream.wait_event(self._slot_ev[self._slot])
+            self._slot_ev[self._slot] = None
+        self._check(self.lib.cc_pok_rlc_partial_device(self.ctx.h, self.n, self.q, self.r, self.nresp,
+                                                       self.base_index, seed, *self._proof_args(),
+                                                       ctypes.c_void_p(self.part.data_ptr()), self._sh),
+                    "cc_pok_rlc_partial_device")
+        self._leave()
+        return self.part
+
+    def per_credential(self) -> np.ndarray:
+        self._enter()
+        self._check(self.lib.cc_pok_verify_batch_device(self.ctx.h, self.n, self.q, self.r, self.nresp,
+                                                        *self._proof_args(),
+                                                        ctypes.c_void_p(self.verdicts.data_ptr()), None, self._sh),
+                    "cc_pok_verify_batch_device")
+        self._leave()
+        return self.verdicts.cpu().numpy()

@@ -40,8 +40,14 @@ class PoKOfSignatureProof:
 
 def pok_verify_batch(ctx: Context, n: int, q: int, revealed_idx, nresp: int, sigma1: bytes, sigma2: bytes,
                      J: bytes, T: bytes, responses: bytes, chal: bytes, revealed_msgs: bytes,
-                     want_gt: bool = False):
-    """Batch PoK verify against the context's params and shared verkey."""
+                     want_gt: bool = False, rlc: bool = False):
+    """Batch PoK verify against the context's params and shared verkey.
+
+    rlc=True checks the whole batch with one random-linear-combination pairing product first
+    (cc_pok_verify_batch_rlc) and falls back to the per-proof path on reject, so the verdicts are the
+    same; it has no GT output."""
+    if rlc and want_gt:
+        raise ValueError("rlc=True has no per-proof GT output (want_gt=True)")
     r = len(revealed_idx)
     sb, ob = ctx.mode.sig_bytes, ctx.mode.other_bytes
     for v, nb, what in ((sigma1, n * sb, "sigma'_1"), (sigma2, n * sb, "sigma'_2"), (J, n * ob, "J"),
@@ -53,9 +59,14 @@ def pok_verify_batch(ctx: Context, n: int, q: int, revealed_idx, nresp: int, sig
     gts = np.zeros(max(n, 1) * GT_BYTES, dtype=np.uint8) if want_gt else None
     keep = [buf(x) for x in (sigma1, sigma2, J, T, responses, chal, revealed_msgs)]
     ptrs = [k[0] for k in keep]
-    st = lib.cc_pok_verify_batch(ctx.h, n, q, r, nresp, ptrs[0], ptrs[1], ptrs[2], ptrs[3], ptrs[4], ptrs[5],
-                                 ctypes.c_void_p(idx.ctypes.data), ptrs[6], ctypes.c_void_p(verdicts.ctypes.data),
-                                 ctypes.c_void_p(gts.ctypes.data) if want_gt else None)
+    if rlc:
+        st = lib.cc_pok_verify_batch_rlc(ctx.h, n, q, r, nresp, ptrs[0], ptrs[1], ptrs[2], ptrs[3], ptrs[4], ptrs[5],
+                                         ctypes.c_void_p(idx.ctypes.data), ptrs[6],
+                                         ctypes.c_void_p(verdicts.ctypes.data))
+    else:
+        st = lib.cc_pok_verify_batch(ctx.h, n, q, r, nresp, ptrs[0], ptrs[1], ptrs[2], ptrs[3], ptrs[4], ptrs[5],
+                                     ctypes.c_void_p(idx.ctypes.data), ptrs[6], ctypes.c_void_p(verdicts.ctypes.data),
+                                     ctypes.c_void_p(gts.ctypes.data) if want_gt else None)
     if st != 0:
         raise CoconutError(st, lib.cc_status_str(st).decode())
     if want_gt:

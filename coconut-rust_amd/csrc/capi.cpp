@@ -96,6 +96,11 @@ int cck_prep_pok(int mode, size_t n, int q, int r, const uint8_t* d_s1, const ui
                  const uint8_t* d_T, const uint8_t* d_resp, const uint8_t* d_chal, const uint8_t* d_rev_msgs,
                  const uint32_t* d_rev_idx, const uint32_t* d_Xaff, uint32_t Xinf, const uint32_t* d_table, int wbits,
                  const uint32_t* d_binf, uint32_t* d_prep, uint32_t* d_flags, uint32_t* d_jtab, hipStream_t st);
+int cck_prep_pok_rlc(int mode, size_t n, size_t ps, int q, int r, uint64_t base_index, const uint32_t* d_key,
+                     const uint8_t* d_J, const uint8_t* d_T, const uint8_t* d_resp, const uint8_t* d_chal,
+                     const uint8_t* d_rev_msgs, const uint32_t* d_rev_idx, const uint32_t* d_table, int wbits,
+                     const uint32_t* d_binf, uint32_t* d_prep, uint32_t* d_flags, uint32_t* d_any, uint32_t* d_jtab,
+                     hipStream_t st);
 int cck_prep_pok_wide(int mode, size_t n, int q, int r, const uint8_t* d_s1, const uint8_t* d_s2, const uint8_t* d_J,
                  const uint8_t* d_T, const uint8_t* d_resp, const uint8_t* d_chal, const uint8_t* d_rev_msgs,
                  const uint32_t* d_rev_idx, const uint32_t* d_Xaff, uint32_t Xinf, const uint32_t* d_table, int wbits,
@@ -252,6 +257,7 @@ struct cc_ctx {
     // identity flags
     DevBuf rlc_pts, rlc_dig, rlc_work, rlc_pw, rlc_finf;
     DevBuf pok_idx;  // revealed indices of the last PoK batch
+    int n_simd = 0;  // SIMDs of the device (4 a CU), read once (pok_rlc_twin)
     // issuer table (cc_set_issuers): sorted ids, decoded verkeys, per-base 8-bit window tables
     size_t iss_n = 0, iss_q = 0;
     std::vector<uint64_t> iss_ids_host;
@@ -276,7 +282,8 @@ struct cc_ctx {
     std::vector<ncclComm_t> comms;
     DevBuf rlc_gath;  // per peer: gathered partials (ndev x RLC_PART_WORDS words)
     // concurrent verify batches (cc_set_concurrency): with K > 1 slots, cc_verify_batch_device /
-    // cc_verify_batch_pervk_device / cc_pok_verify_batch_device / cc_rlc_partial_device calls take the
+    // cc_verify_batch_pervk_device / cc_pok_verify_batch_device / cc_rlc_partial_device /
+    // cc_pok_rlc_partial_device calls take the
     // slots round-robin and are ordered only after the context's earlier work (tables, params) and the
     // same slot's previous batch, so K batches on K caller streams overlap (slots.h).  pool.recs[0] is
     // the context's own workspaces (prep / flags / fbuf / vkb / scratch / pok_idx / wide_*); vslots
@@ -927,10 +934,13 @@ static RlcWork ctx_rlc_work(cc_ctx* c) {
     return {&c->prep, &c->flags, &c->fbuf, &c->scratch, &c->rlc_key, &c->rlc_any, &c->rlc_pts, &c->rlc_dig, &c->rlc_work};
 }
 // sizes for n credentials; a concurrency slot whose buffers must grow waits for its last batch first
-static int rlc_ensure(cc_ctx* c, const RlcWork& r, size_t n, SlotPool::Rec* sl) {
-    const size_t PS = (n + 1) / 2, N = (n + 3) / 4;
+// (scr_min: the PoK partial's tables of d J, which share the scratch with the product tree)
+// twin: the two-proof Miller loop's (n + 1) / 2 Miller values instead of the four-proof loop's
+static int rlc_ensure(cc_ctx* c, const RlcWork& r, size_t n, SlotPool::Rec* sl, size_t scr_min = 0,
+                      bool twin = false) {
+    const size_t PS = (n + 1) / 2, N = twin ? PS : (n + 3) / 4;
     const size_t prep_b = (size_t)PREP_SLOTS * 12 * 4 * std::max(PS, n), flags_b = n * 4, fbuf_b = N * 144 * 4,
-                 scr_b = ((N + 1) / 2) * 144 * 4 + n * 12 * 4 * 72, pts_b = n * 48 * 4, dig_b = 16 * n,
+                 scr_b = std::max(((N + 1) / 2) * 144 * 4 + n * 12 * 4 * 72, scr_min), pts_b = n * 48 * 4, dig_b = 16 * n,
                  work_b = cck_fold_words(c->mode, n) * 4;
     const bool grow = r.prep->bytes < prep_b || r.flags->bytes < flags_b || r.fbuf->bytes < fbuf_b ||
                       r.scratch->bytes < scr_b || r.key->bytes < 32 || r.any->bytes < 4 || r.pts->bytes < pts_b ||
@@ -942,11 +952,38 @@ static int rlc_ensure(cc_ctx* c, const RlcWork& r, size_t n, SlotPool::Rec* sl) 
            r.work->ensure(work_b);
 }
 
+// The PoK form of the partial (pok_rlc.hip): part 1 is the PoK prep (Schnorr check, J's subgroup test,
+// delta J') instead of the delta-scaled message MSM; its tables of d J live in the scratch, which the
+// product tree takes over after the Miller loop.
+struct PokRlcArgs {
+    size_t r;
+    const uint8_t *d_J, *d_T, *d_resp, *d_chal, *d_rev_msgs;
+    const uint32_t* d_idx;
+    bool twin;  // pok_rlc_twin
+};
+// The PoK partial's Miller launch.  The four-proof loop (k_miller4) runs one wave a SIMD and fills the
+// chip only from 128 proofs a SIMD on (131,072 on 1,024 SIMDs); a batch of half that leaves every
+// second SIMD idle for the whole loop.  While the two-proof loop's waves (64 proofs each) still fit one
+// a SIMD it is the shorter launch: the same twin layout, twice the Miller values for the product tree.
+static bool pok_rlc_twin(cc_ctx* c, size_t n) {
+    if (!c->n_simd) {
+        int cu = 0;
+        if (hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess || cu <= 0) {
+            (void)hipGetLastError();
+            cu = 256;
+        }
+        c->n_simd = 4 * cu;
+    }
+    return (n + 63) / 64 <= (size_t)c->n_simd;
+}
+
 static cc_status launch_rlc_partial(cc_ctx* c, const RlcWork& w, size_t n, size_t q, uint64_t base_index,
                                     const uint8_t* seed32, const uint8_t* d_s1, const uint8_t* d_s2,
-                                    const uint8_t* d_msgs, uint32_t* d_partial, hipStream_t st, Staging* stage) {
+                                    const uint8_t* d_msgs, uint32_t* d_partial, hipStream_t st, Staging* stage,
+                                    const PokRlcArgs* pok = nullptr) {
     const size_t PS = (n + 1) / 2;  // prep SoA stride (the twin layout: credentials 2 t, 2 t + 1 at element t)
-    const size_t N = (n + 3) / 4;   // Miller values (four credentials' pairs each, k_miller4)
+    const bool twin = pok && pok->twin;
+    const size_t N = twin ? PS : (n + 3) / 4;  // Miller values (four credentials' pairs each, k_miller4)
     if (stage) {  // a concurrency slot: through its pinned ring, so the host does not wait for the stream
         KCK(stage->upload(w.key->p, seed32, 32, st));
     } else {  // pageable source: the copy is staged before the call returns
@@ -980,15 +1017,37 @@ static cc_status launch_rlc_partial(cc_ctx* c, const RlcWork& w, size_t n, size_
         HIPCK(hipStreamWaitEvent(side, c->ev_fork, 0));
     }
     KCK(cck_fold_window(c->mode, n, w.work->as<uint32_t>(), d_partial, side));
-    KCK(prep_part(1));  // delta X~ + sum (delta m_j) Y~_j
+    if (pok)  // Schnorr check, J's subgroup test, delta X~ + sum_revealed (delta m_i) Y~_i + delta J
+        KCK(cck_prep_pok_rlc(c->mode, n, PS, (int)q, (int)pok->r, base_index, w.key->as<uint32_t>(), pok->d_J, pok->d_T,
+                             pok->d_resp, pok->d_chal, pok->d_rev_msgs, pok->d_idx, c->table.as<uint32_t>(), c->wbits,
+                             c->table_inf.as<uint32_t>(), w.prep->as<uint32_t>(), w.flags->as<uint32_t>(),
+                             w.any->as<uint32_t>(), w.scratch->as<uint32_t>(), st));
+    else
+        KCK(prep_part(1));  // delta X~ + sum (delta m_j) Y~_j
     if (c->timing) (void)hipEventRecord(c->ev[1], st);
     // SigG2: sigma_1's subgroup test comes from this loop's T (a failure raises rlc_any: fallback)
-    KCK(cck_miller_quad(c->mode, n, PS, w.prep->as<uint32_t>(), w.flags->as<uint32_t>(), w.fbuf->as<uint32_t>(), N,
-                        c->mode == 0 ? w.any->as<uint32_t>() : nullptr, st));
+    bool joined = false;
+    if (twin && side != st) {
+        // one wave a SIMD holds only if every CU is free when the loop's blocks are placed: the window
+        // sums' 16 waves, where they outlast the prep (SigG1), pushed blocks onto occupied CUs, and the
+        // launch then took the two-wave time (12.3 ms against 8.1).  Join the side stream first.
+        HIPCK(hipEventRecord(c->ev_join, side));
+        HIPCK(hipStreamWaitEvent(st, c->ev_join, 0));
+        joined = true;
+    }
+    if (twin)  // two proofs per loop (k_miller<SIG, true>; the constant operand is unused)
+        KCK(c->mode == 0 ? cck_miller_lz_g2(1, n, PS, w.prep->as<uint32_t>(), w.flags->as<uint32_t>(),
+                                            c->gtilde_lz.as<uint32_t>(), w.fbuf->as<uint32_t>(), N, 0,
+                                            w.any->as<uint32_t>(), st)
+                         : cck_miller_lz_g1(1, n, PS, w.prep->as<uint32_t>(), w.flags->as<uint32_t>(),
+                                            c->gtilde_lines.as<uint32_t>(), w.fbuf->as<uint32_t>(), N, 0, nullptr, st));
+    else
+        KCK(cck_miller_quad(c->mode, n, PS, w.prep->as<uint32_t>(), w.flags->as<uint32_t>(), w.fbuf->as<uint32_t>(), N,
+                            c->mode == 0 ? w.any->as<uint32_t>() : nullptr, st));
     if (c->timing) (void)hipEventRecord(c->ev[2], st);
     KCK(cck_rlc_reduce(N, w.fbuf->as<uint32_t>(), w.scratch->as<uint32_t>(), w.any->as<uint32_t>(), d_partial,
                        st));
-    if (side != st) {  // the window section is part of the partial: the call ends when both are written
+    if (side != st && !joined) {  // the window section is part of the partial: the call ends when both are written
         HIPCK(hipEventRecord(c->ev_join, side));
         HIPCK(hipStreamWaitEvent(st, c->ev_join, 0));
     }
@@ -996,6 +1055,22 @@ static cc_status launch_rlc_partial(cc_ctx* c, const RlcWork& w, size_t n, size_
         (void)hipEventRecord(c->ev[3], st);
         collect_timing(c);
     }
+    return CC_OK;
+}
+
+// an empty shard (a batch smaller than the rank count): the neutral partial — Fp12 one (Montgomery one
+// in slot 0, zeros elsewhere), a clear fall-back flag and 16 identity window sums — so every rank still
+// joins the all-gather and the product over ranks is unchanged
+static cc_status write_neutral_partial(uint32_t* d_partial, hipStream_t st) {
+    static const uint32_t kOne[12] = {0x03a9fb84u, 0xc57400d2u, 0x629c4a23u, 0x6147acdeu, 0x7e6d26cbu, 0x6b0f4b0bu,
+                                      0xc2b7d6e1u, 0x91ecbde7u, 0x4fdd80b8u, 0xd56a23c3u, 0xf3a0d636u, 0x13317c30u};
+    static const std::vector<uint32_t> kNeutral = [] {
+        std::vector<uint32_t> v(RLC_PART_WORDS, 0u);
+        memcpy(v.data(), kOne, sizeof(kOne));
+        for (int w = 0; w < RLC_WINDOWS; w++) v[RLC_WIN_OFF + RLC_WIN_WORDS * w + 48] = 1u;
+        return v;
+    }();
+    HIPCK(hipMemcpyAsync(d_partial, kNeutral.data(), RLC_PART_WORDS * 4, hipMemcpyHostToDevice, st));
     return CC_OK;
 }
 
@@ -1009,21 +1084,7 @@ cc_status cc_rlc_partial_device(cc_ctx* c, size_t n, size_t q, uint64_t base_ind
     if (q != c->q) return CC_ERR_LEN;
     HIPCK(hipSetDevice(c->device));
     hipStream_t st = stream ? (hipStream_t)stream : c->stream;
-    if (!n) {
-        // empty shard (a batch smaller than the rank count): the neutral partial — Fp12 one (Montgomery
-        // one in slot 0, zeros elsewhere), a clear fall-back flag and 16 identity window sums — so every
-        // rank still joins the all-gather and the product over ranks is unchanged
-        static const uint32_t kOne[12] = {0x03a9fb84u, 0xc57400d2u, 0x629c4a23u, 0x6147acdeu, 0x7e6d26cbu, 0x6b0f4b0bu,
-                                          0xc2b7d6e1u, 0x91ecbde7u, 0x4fdd80b8u, 0xd56a23c3u, 0xf3a0d636u, 0x13317c30u};
-        static const std::vector<uint32_t> kNeutral = [] {
-            std::vector<uint32_t> v(RLC_PART_WORDS, 0u);
-            memcpy(v.data(), kOne, sizeof(kOne));
-            for (int w = 0; w < RLC_WINDOWS; w++) v[RLC_WIN_OFF + RLC_WIN_WORDS * w + 48] = 1u;
-            return v;
-        }();
-        HIPCK(hipMemcpyAsync(d_partial, kNeutral.data(), RLC_PART_WORDS * 4, hipMemcpyHostToDevice, st));
-        return CC_OK;
-    }
+    if (!n) return write_neutral_partial(d_partial, st);
     if (c->concurrency > 1) {  // the next concurrency slot (cc_set_concurrency): its own workspaces
         int k = 0;
         VerifyWork w;
@@ -1796,10 +1857,63 @@ cc_status cc_pok_verify_batch_device(cc_ctx* c, size_t n, size_t q, size_t r, si
     return CC_OK;
 }
 
-cc_status cc_pok_verify_batch(cc_ctx* c, size_t n, size_t q, size_t r, size_t nresp, const uint8_t* s1,
-                              const uint8_t* s2, const uint8_t* J, const uint8_t* T, const uint8_t* resp,
-                              const uint8_t* chal, const uint64_t* rev_idx, const uint8_t* rev_msgs,
-                              uint8_t* verdicts, uint8_t* gt) {
+// The PoK form of cc_rlc_partial_device (pok_rlc.hip): arguments and errors of
+// cc_pok_verify_batch_device, slots and ordering of cc_rlc_partial_device.
+cc_status cc_pok_rlc_partial_device(cc_ctx* c, size_t n, size_t q, size_t r, size_t nresp, uint64_t base_index,
+                                    const uint8_t* seed32, const uint8_t* d_s1, const uint8_t* d_s2,
+                                    const uint8_t* d_J, const uint8_t* d_T, const uint8_t* d_resp,
+                                    const uint8_t* d_chal, const uint64_t* rev_idx, const uint8_t* d_rev_msgs,
+                                    uint32_t* d_partial, void* stream) {
+    c = primary(c);  // a device set forwards to its first device
+    if (!c || !seed32 || !d_partial ||
+        (n && (!d_s1 || !d_s2 || !d_J || !d_T || !d_chal || (nresp && !d_resp) || (r && (!rev_idx || !d_rev_msgs)))))
+        return CC_ERR_DECODE;
+    if (!c->have_params || !c->have_vk) return CC_ERR_STATE;
+    if (q != c->q) return CC_ERR_LEN;
+    std::vector<uint32_t> idx;
+    cc_status s = check_revealed(q, r, rev_idx, idx);
+    if (s) return s;
+    if (nresp != q - r + 1) return CC_ERR_BASES_EXPS;
+    if (n > kMaxBatch) return CC_ERR_DECODE;
+    HIPCK(hipSetDevice(c->device));
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    if (!n) return write_neutral_partial(d_partial, st);
+    const size_t jtab_b = (n * 15 * 84 + 72 * 12) * 4;  // the tables of d J (ensure_work)
+    PokRlcArgs pok{r, d_J, d_T, d_resp, d_chal, d_rev_msgs, nullptr, pok_rlc_twin(c, n)};
+    if (c->concurrency > 1) {  // the next concurrency slot (cc_set_concurrency): its own workspaces
+        int k = 0;
+        VerifyWork w;
+        s = slot_begin(c, st, cc::slots::verify_sizes(n, 0, jtab_b, idx.size() * 4 + 4), k, w);
+        if (s) return s;
+        SlotFence fence(c->pool, c->dev, k, st);
+        VerifySlot* sl = k ? c->vslots[(size_t)k - 1] : nullptr;
+        RlcWork rw = sl ? RlcWork{&sl->prep, &sl->flags, &sl->fbuf, &sl->scratch, &sl->rkey, &sl->rany, &sl->rpts,
+                                  &sl->rdig, &sl->rwork}
+                        : ctx_rlc_work(c);
+        if (rlc_ensure(c, rw, n, &c->pool.recs[(size_t)k], jtab_b, pok.twin)) return CC_ERR_HIP;
+        if (r) KCK(c->stage[(size_t)k].upload(w.idx->p, idx.data(), idx.size() * 4, st));  // pinned ring
+        pok.d_idx = w.idx->as<uint32_t>();
+        s = launch_rlc_partial(c, rw, n, q, base_index, seed32, d_s1, d_s2, nullptr, d_partial, st,
+                               &c->stage[(size_t)k], &pok);
+        if (s) return s;
+        return fence.close() ? CC_ERR_HIP : CC_OK;
+    }
+    drain_slots(c);  // concurrent batches (cc_set_concurrency) may still use the buffers sized below
+    s = ensure_work(c, n);
+    if (s) return s;
+    RlcWork rw = ctx_rlc_work(c);
+    if (rlc_ensure(c, rw, n, nullptr, jtab_b, pok.twin)) return CC_ERR_HIP;
+    StreamOrder order(c, st);
+    if (c->pok_idx.ensure(idx.size() * 4)) return CC_ERR_HIP;
+    HIPCK(hipMemcpyAsync(c->pok_idx.p, idx.data(), idx.size() * 4, hipMemcpyHostToDevice, st));
+    pok.d_idx = c->pok_idx.as<uint32_t>();
+    return launch_rlc_partial(c, rw, n, q, base_index, seed32, d_s1, d_s2, nullptr, d_partial, st, nullptr, &pok);
+}
+
+// the host forms: one upload, then (rlc) the whole-batch check first, the per-proof path on reject
+static cc_status pok_host(cc_ctx* c, size_t n, size_t q, size_t r, size_t nresp, const uint8_t* s1, const uint8_t* s2,
+                          const uint8_t* J, const uint8_t* T, const uint8_t* resp, const uint8_t* chal,
+                          const uint64_t* rev_idx, const uint8_t* rev_msgs, uint8_t* verdicts, uint8_t* gt, int rlc) {
     c = primary(c);  // a device set forwards to its first device
     if (!c || (n && (!s1 || !s2 || !J || !T || !chal || !verdicts || (nresp && !resp) || (r && (!rev_idx || !rev_msgs)))))
         return CC_ERR_DECODE;
@@ -1837,6 +1951,25 @@ cc_status cc_pok_verify_batch(cc_ctx* c, size_t n, size_t q, size_t r, size_t nr
         HIPCK(hipMemcpyAsync(dM.p, rev_msgs, n * r * 48, hipMemcpyHostToDevice, st));
         HIPCK(hipMemcpyAsync(dI.p, idx.data(), r * 4, hipMemcpyHostToDevice, st));
     }
+    if (rlc) {
+        // whole-batch check; on reject (a bad proof, an identity sigma' or a J outside the subgroup
+        // somewhere) fall through to the per-proof path so every verdict equals the reference's
+        uint8_t seed[32], accept = 0;
+        if (fresh_seed(seed)) return CC_ERR_HIP;
+        if (c->rlc_part.ensure(RLC_PART_WORDS * 4) || c->rlc_accept.ensure(1)) return CC_ERR_HIP;
+        s = cc_pok_rlc_partial_device(c, n, q, r, nresp, 0, seed, c->in_s1.as<uint8_t>(), c->in_s2.as<uint8_t>(),
+                                      dJ.as<uint8_t>(), dT.as<uint8_t>(), dR.as<uint8_t>(), dC.as<uint8_t>(), rev_idx,
+                                      dM.as<uint8_t>(), c->rlc_part.as<uint32_t>(), st);
+        if (s) return s;
+        s = cc_rlc_finish_device(c, 1, c->rlc_part.as<uint32_t>(), c->rlc_accept.as<uint8_t>(), nullptr, st);
+        if (s) return s;
+        HIPCK(hipMemcpyAsync(&accept, c->rlc_accept.p, 1, hipMemcpyDeviceToHost, st));
+        HIPCK(hipStreamSynchronize(st));
+        if (accept) {
+            memset(verdicts, 1, n);
+            return CC_OK;
+        }
+    }
     s = launch_pok(c, ctx_work(c), n, q, r, c->in_s1.as<uint8_t>(), c->in_s2.as<uint8_t>(), dJ.as<uint8_t>(), dT.as<uint8_t>(),
                    dR.as<uint8_t>(), dC.as<uint8_t>(), dI.as<uint32_t>(), dM.as<uint8_t>(), c->verdicts.as<uint8_t>(),
                    gt ? c->gt.as<uint8_t>() : nullptr, st);
@@ -1846,6 +1979,20 @@ cc_status cc_pok_verify_batch(cc_ctx* c, size_t n, size_t q, size_t r, size_t nr
     HIPCK(hipStreamSynchronize(st));
     collect_timing(c);
     return CC_OK;
+}
+
+cc_status cc_pok_verify_batch(cc_ctx* c, size_t n, size_t q, size_t r, size_t nresp, const uint8_t* s1,
+                              const uint8_t* s2, const uint8_t* J, const uint8_t* T, const uint8_t* resp,
+                              const uint8_t* chal, const uint64_t* rev_idx, const uint8_t* rev_msgs,
+                              uint8_t* verdicts, uint8_t* gt) {
+    return pok_host(c, n, q, r, nresp, s1, s2, J, T, resp, chal, rev_idx, rev_msgs, verdicts, gt, 0);
+}
+
+cc_status cc_pok_verify_batch_rlc(cc_ctx* c, size_t n, size_t q, size_t r, size_t nresp, const uint8_t* s1,
+                                  const uint8_t* s2, const uint8_t* J, const uint8_t* T, const uint8_t* resp,
+                                  const uint8_t* chal, const uint64_t* rev_idx, const uint8_t* rev_msgs,
+                                  uint8_t* verdicts) {
+    return pok_host(c, n, q, r, nresp, s1, s2, J, T, resp, chal, rev_idx, rev_msgs, verdicts, nullptr, 1);
 }
 
 

@@ -135,7 +135,8 @@ cc_status cc_verify_batch_pervk_device(cc_ctx* ctx, size_t n, size_t q, const ui
                                        void* stream);
 
 /* Concurrent verify batches on one context: with `slots` = K > 1, cc_verify_batch_device,
- * cc_verify_batch_pervk_device, cc_pok_verify_batch_device and cc_rlc_partial_device calls take K
+ * cc_verify_batch_pervk_device, cc_pok_verify_batch_device, cc_rlc_partial_device and
+ * cc_pok_rlc_partial_device calls take K
  * workspace slots round-robin (each slot its own prep SoA, flags, Miller values, PoK d J tables and RLC
  * delta/fold buffers; the verkey tables are shared)
  * and are ordered only after the context's earlier work (tables, params) and the same slot's previous
@@ -248,6 +249,35 @@ cc_status cc_pok_verify_batch_device(cc_ctx* ctx, size_t n, size_t q, size_t r, 
                                      const uint8_t* d_responses, const uint8_t* d_chal, const uint64_t* revealed_idx,
                                      const uint8_t* d_revealed_msgs, uint8_t* d_verdicts, uint8_t* d_gt_or_null,
                                      void* stream);
+
+/* RLC batch mode for PoKOfSignatureProof::verify (shared verkey).  The proof's pairing equation
+ * e(sigma'_1, J') * e(-sigma'_2, g~) == 1, J' = X~ + J + sum_revealed m_i Y~_i, has the shape of
+ * Signature::verify's, so a batch is checked as one delta-weighted pairing product, with the
+ * deltas, the partial format and the finish of the RLC block above; the Schnorr relation costs no
+ * pairing and is checked per proof, exactly.  Contract: a batch is accepted only if every proof's
+ * Schnorr relation holds exactly and the delta-weighted pairing product is one; a forged batch passes
+ * with probability <= 2^-127.  A sigma' that is the identity or outside the subgroup, a J outside the
+ * subgroup, a failed Schnorr relation or a verkey / g~ outside the subgroup raise the partial's
+ * fall-back flag: the finish then rejects and the caller verifies per proof, so verdicts never change.
+ *   cc_pok_rlc_partial_device: arguments and errors of cc_pok_verify_batch_device, deltas =
+ *                              ChaCha20(seed32, base_index + i); d_partial: CC_RLC_PARTIAL_WORDS x u32
+ *                              device buffer, finished by cc_rlc_finish_device, alone or with the partials
+ *                              of the other shards of the same PoK batch; n = 0 writes the neutral
+ *                              partial.  Asynchronous on `stream` (NULL: the context stream); takes a
+ *                              concurrency slot as cc_rlc_partial_device does (cc_set_concurrency).
+ *   cc_pok_verify_batch_rlc  : cc_pok_verify_batch without the GT output: one upload, partial + finish
+ *                              with a fresh seed from /dev/urandom; all-ones verdicts on accept, else
+ *                              the per-proof path on the buffers already on the device.  Verdicts always
+ *                              equal cc_pok_verify_batch's. */
+cc_status cc_pok_rlc_partial_device(cc_ctx* ctx, size_t n, size_t q, size_t r, size_t nresp, uint64_t base_index,
+                                    const uint8_t* seed32, const uint8_t* d_sigma1, const uint8_t* d_sigma2,
+                                    const uint8_t* d_J, const uint8_t* d_T, const uint8_t* d_responses,
+                                    const uint8_t* d_chal, const uint64_t* revealed_idx,
+                                    const uint8_t* d_revealed_msgs, uint32_t* d_partial, void* stream);
+cc_status cc_pok_verify_batch_rlc(cc_ctx* ctx, size_t n, size_t q, size_t r, size_t nresp, const uint8_t* sigma1,
+                                  const uint8_t* sigma2, const uint8_t* J, const uint8_t* T, const uint8_t* responses,
+                                  const uint8_t* chal, const uint64_t* revealed_idx, const uint8_t* revealed_msgs,
+                                  uint8_t* verdicts);
 
 /* Codec check: decode n encodings of `group` (1 = G1 97 B, 2 = G2 192 B) and
  * report per point 0 = identity (AMCL maps a bad prefix / off-curve point to infinity), 1 = on the
