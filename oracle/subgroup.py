@@ -18,6 +18,9 @@ from . import bls12_381 as B
 
 P, R = B.P, B.R
 X = -0xD201000000010000
+# cofactors: #E(Fp) = H1 r with H1 = (x - 1)^2 / 3 = 3 * 11^2 * ..., #E'(Fp2) = H2 r with H2 = 13^2 * 23^2 * ...
+H1 = 0x396C8C005555E1568C00AAAB0000AAAB
+H2 = 0x5D543A95414E7F1091D50792876A202CD91DE4547085ABAA68A205B2E5A7DDFA628F1CB4D9E82EF21537E293A6691AE1616EC6E786F0C70CF1C38E31C7238E5
 
 # the two primitive cube roots of unity in Fp; phi with the right one acts as [-x^2] on G1
 _w = pow(2, (P - 1) // 3, P)

@@ -334,6 +334,63 @@ def make_subgroup(seed):
     return out
 
 
+def make_torsion(seed):
+    """Curve points of small order outside G1 / G2 (tests/torsion_edges.py): [h r / l^k] of a random curve
+    point, reduced to order exactly l.  Each record carries its order (hex) and, for a mixed point
+    k G + T, the scalar k.  Orders are checked here by the definition."""
+    from oracle import subgroup as S
+    rng = C.Drbg(seed)
+
+    def torsion(curve, h, ell):
+        """A point of order exactly ell from the ell-part of the cofactor h."""
+        e = 0
+        while h % ell ** (e + 1) == 0:
+            e += 1
+        assert e >= 1
+        while True:
+            T = curve.mul_any(S.random_curve_point(curve, rng.fr()), h * B.R // ell ** e)
+            while T is not None and curve.mul_any(T, ell) is not None:
+                T = curve.mul_any(T, ell)
+            if T is not None:
+                return T
+
+    def multiples(curve, T, m):
+        return [curve.mul_any(T, k) for k in range(m)]
+
+    def rec(name, enc, curve, Pt, order, k=None):
+        assert curve.on_curve(Pt) and curve.mul_any(Pt, order) is None
+        for ell in (3, 11, 13, 23, B.R):
+            if order % ell == 0:
+                assert curve.mul_any(Pt, order // ell) is not None, (name, ell)
+        r = {"name": name, "point": hx(enc(Pt)), "order": format(order, "x")}
+        if k is not None:
+            r["k"] = fr_hex(k)
+        return r
+
+    G2c, G1c = B.G2, B.G1
+    T13 = torsion(G2c, S.H2, 13)
+    while True:
+        T13b = torsion(G2c, S.H2, 13)
+        if T13b not in multiples(G2c, T13, 13):
+            break
+    T23 = torsion(G2c, S.H2, 23)
+    k1, k2 = rng.fr(), rng.fr()
+    e2 = B.g2_to_bytes
+    g2 = [rec("T13", e2, G2c, T13, 13), rec("T13b", e2, G2c, T13b, 13), rec("T23", e2, G2c, T23, 23),
+          rec("T13+T23", e2, G2c, G2c.add(T13, T23), 299),
+          rec("kG+T13", e2, G2c, G2c.add(G2c.mul(G2c.gen, k1), T13), 13 * B.R, k1),
+          rec("k2G+T13", e2, G2c, G2c.add(G2c.mul(G2c.gen, k2), T13), 13 * B.R, k2),
+          rec("-T13", e2, G2c, G2c.neg(T13), 13)]
+    T3, T11 = (0, 2), torsion(G1c, S.H1, 11)
+    k3, k4 = rng.fr(), rng.fr()
+    e1 = B.g1_to_bytes
+    g1 = [rec("T3", e1, G1c, T3, 3), rec("-T3", e1, G1c, G1c.neg(T3), 3), rec("T11", e1, G1c, T11, 11),
+          rec("kG+T11", e1, G1c, G1c.add(G1c.mul(G1c.gen, k3), T11), 11 * B.R, k3),
+          rec("kG+T3", e1, G1c, G1c.add(G1c.mul(G1c.gen, k4), T3), 3 * B.R, k4)]
+    print(f"  torsion: G2 {[r['name'] for r in g2]}, G1 {[r['name'] for r in g1]}", flush=True)
+    return {"seed": seed, "G1": g1, "G2": g2}
+
+
 def make_hash_to_curve():
     """amcl_wrapper from_msg_hash vectors (PARITY UNPINNED: AMCL mapit restated, oracle/hash_to_curve.py):
     messages across the SHAKE256 block boundary (rate 136) and Params::new(6, "test") in both group
@@ -483,6 +540,8 @@ def main():
         write("hash_to_curve.json", make_hash_to_curve())
     if want("subgroup"):
         write("subgroup.json", make_subgroup(13))
+    if want("torsion"):
+        write("torsion.json", make_torsion(41))
     for mode in ("G2", "G1"):
         if want("verify"):
             write(f"verify_{mode.lower()}_q6.json", make_verify(mode, 6, 30, 2))

@@ -5,15 +5,18 @@ logarithm known, and a model of the order in which each kernel adds its table en
 Plain Python over integers plus the C oracle's oc_gen_mul / oc_msm (points from scalars); no product code
 and no context.  Chain, join and the constants come from tests/fixed_edges.py.
 
-POINTS.  Every base is a known multiple of the generator, or, in G1, of the order-3 point T = (0, 2) of
-y^2 = x^3 + 4 (2 T = -T = (0, -2)), which g1_decode accepts: it checks the curve equation, not the
-subgroup.  A point a G + b T is the integer v mod 3 r with v = a mod r and v = b mod 3 (the Chinese
-remainder theorem: Z_3r = Z_r x Z_3), so equality, negation and the identity are what they are in the
-group, and a scalar acts by integer multiplication.  For T the multiples 3 T and 6 T are the identity
-(flagged in the table and skipped in the walk) and the table build's 5 T = 4 T + T = T + T comes from the
-doubling branch of the mixed addition.  G2 has no analogue: the twist's cofactor has no prime factor
-below 13, so no G2 point of small order can be written down, and a base of large unknown order outside
-the subgroup behaves like any other base.  G2 is left without one.
+POINTS.  Every base is a known multiple of the generator, or of the group's small-order base T of order
+ORDER[group]: in G1 the order-3 point (0, 2) of y^2 = x^3 + 4 (2 T = -T = (0, -2)), in G2 the order-13 point
+T13 of tests/golden/torsion.json (the twist's cofactor is divisible by 13^2); the decoders accept both: they
+check the curve equation, not the subgroup.  A point a G + b T is the integer v mod M = 39 r with v = a mod r
+and v = b mod the order of T (the Chinese remainder theorem: Z_39r = Z_r x Z_3 x Z_13; a G1 point has no
+part mod 13 and a G2 point none mod 3), so equality, negation and the identity are what they are in the
+group, and a scalar acts by integer multiplication.  For the order-3 base the multiples 3 T and 6 T are the
+identity (flagged in the table and skipped in the walk) and the table build's 5 T = 4 T + T = T + T comes
+from the doubling branch of the mixed addition.  The order-13 base's table 1 T .. 8 T meets neither (no
+multiple below 13 is the identity, and k T = +-T needs k = 12 or 14), so in G2 the build stays on the general
+branch; what the order-13 rows add is a small-order base in every G2 walk and join, whose sums (and, in
+SigG1 verify, the Miller loop over a pr of order 13 r) the oracle pins.
 
 DIGITS.  recode_w4 restates straus.h: 64 nibbles with a carry, digit v - 16 if v > 8, and a 65th digit
 that is the last carry.  Two facts follow from the code, and tests/test_straus_edges_model.py asserts them:
@@ -45,6 +48,7 @@ Lagrange coefficients included.
 """
 import ctypes
 import functools
+import json
 import math
 import os
 import random
@@ -54,11 +58,26 @@ import fixed_edges as F
 from fixed_edges import (CHAIN, G1_GENERATOR, G1_IDENTITY, G2_GENERATOR, G2_IDENTITY, JOIN, R, Chain, be48,  # noqa: F401
                          join)
 
-M = 3 * R
-GEN = 3 * pow(3, -1, R) % M  # the generator: 1 mod r, 0 mod 3
-T3 = R * pow(R, -1, 3) % M  # the order-3 point (0, 2): 0 mod r, 1 mod 3
+ORDER = {1: 3, 2: 13}  # the order of each group's small-order base
+M = 3 * 13 * R
+
+
+def _crt_unit(m):
+    """1 mod m, 0 mod M / m"""
+    return (M // m) * pow(M // m, -1, m) % M
+
+
+GEN = _crt_unit(R)  # the generator: 1 mod r, 0 mod 39
+TORSION = {ell: _crt_unit(ell) for ell in ORDER.values()}  # the base of order ell: 1 mod ell, 0 mod M / ell
+T3, T13 = TORSION[3], TORSION[13]  # (0, 2) in G1; T13 of tests/golden/torsion.json in G2
 G1_ORDER3 = b"\x04" + bytes(48) + (2).to_bytes(48, "big")
 G1_ORDER3_NEG = b"\x04" + bytes(48) + (F.P - 2).to_bytes(48, "big")
+
+
+@functools.lru_cache(maxsize=None)
+def g2_order13():
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "torsion.json")) as f:
+        return next(bytes.fromhex(r["point"]) for r in json.load(f)["G2"] if r["name"] == "T13")
 HLOG = random.Random(0xC0C0).randrange(1 << 250, R)  # stands in for the unknown logarithm of a hashed point
 WALK = "skipped-doublings"
 
@@ -236,7 +255,7 @@ def steer(layout, logs, scalars, j, sign):
     """A log for base j whose first addition meets sign x the accumulator (None if that is empty)."""
     part = next(p for p in partition(layout, len(logs)) if j in p)
     hit = walk([(logs[k], digits(scalars[k])) for k in part], stop_at=part.index(j))
-    if not hit or not hit[0] or hit[0] % 3:
+    if not hit or not hit[0] or hit[0] % (M // R):
         return None
     return sub(sign * hit[0] * pow(hit[1], -1, R))
 
@@ -244,7 +263,7 @@ def steer(layout, logs, scalars, j, sign):
 def steer_sum(logs, scalars, part, j, target):
     """A log for base j of `part` so that the part's sum is `target` (a subgroup point)."""
     rest = sum((scalars[k] % R) * logs[k] for k in part if k != j) % M
-    if rest % 3 or target % 3 or not scalars[j] % R:
+    if rest % (M // R) or target % (M // R) or not scalars[j] % R:
         return None
     return sub((target - rest) * pow(scalars[j] % R, -1, R))
 
@@ -255,6 +274,8 @@ def msm_cases(layout, scalars, seed, opaque=None, with_x=False):
     opaque: {index: stand-in log} of bases the caller cannot choose (a hashed point); their lanes take no
     part in any steering."""
     t, g1 = len(scalars), layout in G1_LAYOUTS
+    ell = ORDER[1 if g1 else 2]
+    tors = TORSION[ell]
     opaque = opaque or {}
     rng = random.Random(seed)
     rnd = lambda: sub(rng.randrange(1 << 200, R))  # noqa: E731
@@ -313,14 +334,15 @@ def msm_cases(layout, scalars, seed, opaque=None, with_x=False):
             k = longest[i]
             case(f"identity_base_{('first', 'middle', 'last')[n] if len(where) == 3 else i}", with_(k, 0), [],
                  off=[k] if n % 2 else [])
-        if g1:
-            case("order3_first", with_(longest[0], T3), [("build", "to-identity"), ("build", "from-identity"),
-                                                         ("build", "doubling")])
-            case("order3_neg_last", with_(longest[-1], 2 * T3), [("build", "doubling")])
+        # the group's small-order base (order 3 in G1, 13 in G2): in G1 its table build 2 T .. 8 T meets the
+        # identity twice and the doubling branch; an order-13 base's meets nothing (8 < 12)
+        case(f"order{ell}_first", with_(longest[0], tors), [("build", "to-identity"), ("build", "from-identity"),
+                                                            ("build", "doubling")] if g1 else [])
+        case(f"order{ell}_neg_last", with_(longest[-1], (ell - 1) * tors), [("build", "doubling")] if g1 else [])
     allz = [0 if k not in opaque else base[k] for k in range(t)]
     case("all_identity", allz, [], off=[k for k in range(1, t, 2) if k not in opaque])
-    if g1:
-        case("all_order3", [T3 if k not in opaque else base[k] for k in range(t)], [("build", "to-identity")])
+    case(f"all_order{ell}", [tors if k not in opaque else base[k] for k in range(t)],
+         [("build", "to-identity")] if g1 else [])
     if with_x:
         s = expected(base, scalars)
         case("x_identity", base, [], xlog=0)
@@ -328,8 +350,7 @@ def msm_cases(layout, scalars, seed, opaque=None, with_x=False):
             case("x_cancels", base, [("chain", "to-identity")], xlog=M - s)
             case("x_equal", base, [("chain", "doubling")], xlog=s)
         case("x_only", allz, [("chain", "fresh")])
-        if g1:
-            case("x_order3", base, [("chain", "general")], xlog=T3)
+        case(f"x_order{ell}", base, [("chain", "general")], xlog=tors)
     return cases
 
 
@@ -453,18 +474,19 @@ def msm(oc, group, pts, scalars):
 
 
 def point_bytes(oc, group, vals, off=()):
-    """Encodings of points given as integers mod 3 r; index in `off`: an off-curve encoding (it decodes to
+    """Encodings of points given as integers mod M = 39 r (of `group`: no part of the other group's small
+    order); index in `off`: an off-curve encoding (it decodes to
     the identity) where the point is the identity."""
     eb = 97 if group == 1 else 192
     ident = G1_IDENTITY if group == 1 else G2_IDENTITY
     raw = F.gen_mul(oc, group, [v % R for v in vals])
     out = []
     for i, v in enumerate(vals):
-        p, b = raw[eb * i:eb * (i + 1)], v % 3
+        p, b = raw[eb * i:eb * (i + 1)], v % ORDER[group]
+        assert v % (M // R) == _crt_unit(ORDER[group]) * b % (M // R), "the other group's small-order part"
         if b:
-            assert group == 1, "no order-3 point in G2"
-            t = G1_ORDER3 if b == 1 else G1_ORDER3_NEG
-            p = t if v % R == 0 else msm(oc, 1, p + t, [1, 1])
+            t = g2_order13() if group == 2 else G1_ORDER3
+            p = msm(oc, group, t, [b]) if v % R == 0 else msm(oc, group, p + t, [1, b])
         elif v % R == 0:
             p = ident
             if i in off:
@@ -478,7 +500,10 @@ def point_bytes(oc, group, vals, off=()):
 def verify_batch_inputs(oc, mode, q):
     """Every case of verify_cases() as a credential and its twin with sigma_2 off by G.  pr = X~ + sum m_j
     Y~_j = s g~; sigma = (k G, k s G).  Valid iff s != 0: an order-3 part b T of pr pairs to
-    one (e(P, T) has order dividing both 3 and r), so it changes neither verdict nor GT.
+    one (e(P, T) has order dividing both 3 and r), so it changes neither verdict nor GT.  In SigG1 pr is the
+    Miller loop's Q side: with an order-13 part it is a point of order 13 r (or 13), on which the loop's value is
+    no pairing; the oracle rejects every such credential (expect 0; the GT bytes still pin the MSM's point,
+    its order-13 part included).
     Returns dict(names, n, s1, s2, msgs, X, Y, g, expect)."""
     og, sg = (1, 2) if mode == 0 else (2, 1)
     gk = verify_gk(mode, q)
@@ -492,7 +517,7 @@ def verify_batch_inputs(oc, mode, q):
             e1.append(k)
             e2.append(k * s + bad)
             names.append(c["name"] + ("/off_by_g" if bad else "/valid"))
-            expect.append(int(not bad and s != 0))
+            expect.append(int(not bad and s != 0 and pr % 13 == 0))
             mb.append(b"".join(be48(m) for m in c["msgs"]))
             base = len(ys)
             offs += [base + j for j in c["off"]]

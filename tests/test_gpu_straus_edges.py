@@ -16,9 +16,14 @@ comparison is byte equality with the C oracle.
   aggregated sigma_2 and a ciphertext in SigG1 (it is part of every G1 case list).  The aggregation and
   blind-signing outputs are the points themselves, so they pin the order-3 part of the sum.  The verify
   outputs cannot: e(P, T) = 1 for a point T of order 3, so a wrong multiple of T in pr changes neither
-  verdict nor GT; there the order-3 cases show only that the rest of the sum is unharmed.
+  verdict nor GT; there the order-3 cases show only that the rest of the sum is unharmed;
+* the G2 order-13 base T13 (tests/golden/torsion.json) wherever G2 is the variable base: a verkey component
+  and X~ in SigG1, an aggregated sigma_2 and a ciphertext in SigG2.  Here verify does pin the small-order
+  part: pr is the Miller loop's Q side, a pr of order 13 r is rejected by the oracle and its GT bytes depend
+  on the order-13 part of the sum.
 
-What the file notices, measured on an MI355X with one branch changed at a time (never committed): the
+What the file notices, measured on an MI355X with one branch changed at a time (never committed), BEFORE the
+G2 case lists gained their order-13 rows; the counts were not measured again with those rows: the
 doubling / to-identity choice flipped in the window walk's mixed addition of straus_g2lz_pair fails 7 of
 these tests (verify, both aggregates, blind signing), in straus_g1lz_lane's 2 (verify), in the table build
 of k_msm_straus<Fp, 16> 12 (every order-3 row).  Two changes it cannot notice, by the arithmetic: the same

@@ -9,9 +9,11 @@ INPUTS that tests/test_gpu_straus_edges.py feeds the device, not on the device.
 * per layout the union of the cases reaches all five chain branches, all five join branches (the
   one-chain layouts lane and pair have no join), a mid-walk round of skipped doublings, and in the table
   build of the G1 layouts the exceptional branches of an order-3 base.  UNREACHABLE BY CONSTRUCTION: the
-  table build in the G2 layouts (pair, wide8, pairsG) takes the general branch alone, since k P = P or -P
-  for k in 2 .. 7 needs a point of order below 13 and the twist has none (straus_edges docstring);
-* the oracle agrees with the constructed expectations: verdicts, aggregated points, the order-3 point.
+  table build in the G2 layouts (pair, wide8, pairsG) takes the general branch alone, since k P = O, P or -P
+  for k in 2 .. 8 needs a point of order below 13 and the twist has none; its order-13 base is in every G2
+  case list all the same (straus_edges docstring), and its rows are asserted present;
+* the oracle agrees with the constructed expectations: verdicts, aggregated points, the order-3 and the
+  order-13 point.
 """
 import ctypes
 import random
@@ -20,7 +22,7 @@ import pytest
 
 import straus_edges as S
 from conftest import host_threads
-from fixed_edges import CHAIN, G1_IDENTITY, JOIN, R, be48, gen_mul
+from fixed_edges import CHAIN, G1_IDENTITY, G2_IDENTITY, JOIN, R, be48, gen_mul
 
 MODES = (0, 1)
 ORDER3 = {"to-identity", "from-identity", "doubling"}
@@ -140,6 +142,34 @@ def test_oracle_on_the_order3_point(oc):
     assert S.point_bytes(oc, 1, [S.T3, 2 * S.T3, 0]) == S.G1_ORDER3 + S.G1_ORDER3_NEG + G1_IDENTITY
     mixed = S.point_bytes(oc, 1, [S.sub(7) + S.T3])
     assert S.msm(oc, 1, mixed, [3]) == gen_mul(oc, 1, [21])
+
+
+def test_order13_table_build_and_rows():
+    """An order-13 base: 2 T .. 8 T all by the general branch (unreachable by construction: module docstring),
+    and every G2 case list holds the order-13 rows next to the G1 lists' order-3 ones."""
+    assert S.table_build(S.T13) == ["general"] * 6 and S.table_build(12 * S.T13) == ["general"] * 6
+    assert all(d * S.T13 % S.M for d in range(1, 9)) and 13 * S.T13 % S.M == 0 and 3 * S.T3 % S.M == 0
+    assert S.T13 % R == 0 and S.T13 % 3 == 0 and S.T13 % 13 == 1 and S.T3 % 13 == 0 and S.GEN % 39 == 0
+    for lay in S.LAYOUTS:
+        ell = 3 if lay in S.G1_LAYOUTS else 13
+        names = {c["name"] for c in S.msm_cases(lay, [5, 6, R - 1, 77, 12345], 1, with_x=True)}
+        assert {f"order{ell}_first", f"order{ell}_neg_last", f"all_order{ell}", f"x_order{ell}"} <= names, (lay, names)
+        other = {3: 13, 13: 3}[ell]  # the other group's small order
+        assert not any(f"order{other}" in n for n in names)
+    for mode in MODES:
+        for q in S.VERIFY_Q:
+            ell = 3 if mode == 0 else 13
+            assert sum(f"order{ell}" in c["name"] for c in S.verify_cases(mode, q)) >= 8
+
+
+def test_oracle_on_the_order13_point(oc):
+    t13 = S.g2_order13()
+    assert S.msm(oc, 2, t13, [13]) == G2_IDENTITY and S.msm(oc, 2, t13, [26]) == G2_IDENTITY
+    assert S.msm(oc, 2, t13, [14]) == t13 and S.msm(oc, 2, t13, [1]) == t13
+    assert S.point_bytes(oc, 2, [S.T13, 0]) == t13 + G2_IDENTITY
+    assert S.point_bytes(oc, 2, [12 * S.T13]) == S.msm(oc, 2, t13, [12])
+    mixed = S.point_bytes(oc, 2, [S.sub(7) + S.T13])
+    assert S.msm(oc, 2, mixed, [13]) == gen_mul(oc, 2, [91])
 
 
 def test_lagrange_matches_the_oracle(oc):
