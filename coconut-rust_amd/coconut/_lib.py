@@ -55,6 +55,12 @@ _SIGS = {
     "cc_pok_rlc_partial_device": (c_int, [c_p, c_sz, c_sz, c_sz, c_sz, ctypes.c_uint64, c_p, c_p, c_p, c_p, c_p,
                                           c_p, c_p, c_p, c_p, c_p, c_p]),
     "cc_pok_verify_batch_rlc": (c_int, [c_p, c_sz, c_sz, c_sz, c_sz, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "cc_pok_init_batch": (c_int, [c_p, c_sz, c_sz, c_sz, c_sz, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "cc_pok_init_batch_device": (c_int, [c_p, c_sz, c_sz, c_sz, c_sz, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
+                                         c_p]),
+    "cc_pok_gen_proof_batch": (c_int, [c_p, c_sz, c_sz, c_sz, c_sz, c_p, c_p, c_p, c_p, c_p]),
+    "cc_pok_gen_proof_batch_device": (c_int, [c_p, c_sz, c_sz, c_sz, c_sz, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "cc_unblind_batch": (c_int, [c_p, c_sz, c_p, c_p, c_p, c_p]),
     "cc_signature_aggregate_batch_device": (c_int, [c_p, c_sz, c_sz, c_sz, c_p, c_p, c_p, c_p, c_p, c_p]),
     "cc_set_issuers": (c_int, [c_p, c_sz, c_sz, c_p, c_p, c_p]),
     "cc_verkey_aggregate_ids": (c_int, [c_p, c_sz, c_sz, c_sz, c_p, c_p, c_p]),

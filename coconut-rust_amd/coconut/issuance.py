@@ -1,6 +1,6 @@
-"""Issuer-side batch entry points — host mirror of reference src/signature.rs:124-444 (SURVEY.md
+"""Issuer-side batch entry points and the holder's BlindSignature::unblind — host mirror of reference src/signature.rs:124-444 (SURVEY.md
 §8(f) row 3): BlindSignature::new (382-433) and SignatureRequestProof::verify (324-377) for whole
-batches of signature requests, through include/coconut_hip.h."""
+batches of signature requests, and BlindSignature::unblind (436-443), through include/coconut_hip.h."""
 from __future__ import annotations
 
 import ctypes
@@ -79,3 +79,21 @@ def vss_verify_batch(ctx: Context, t: int, g: bytes, h: bytes, commitment_sets: 
                                   ctypes.c_void_p(so.ctypes.data), ctypes.c_void_p(iv.ctypes.data), keep[3][0],
                                   ctypes.c_void_p(v.ctypes.data)), "cc_vss_verify_batch")
     return v[:n]
+
+
+def unblind_batch(ctx: Context, c1s: Sequence[bytes], c2s: Sequence[bytes], sks: Sequence[bytes]) -> List[bytes]:
+    """BlindSignature::unblind per row: sigma_2 = c~2 - sk * c~1 with that row's ElGamal secret key
+    (48 B big-endian); sigma_1 is the blind signature's h."""
+    n = len(c1s)
+    sb = ctx.mode.sig_bytes
+    if len(c2s) != n or len(sks) != n:
+        raise ValueError("c1s, c2s and sks must have one entry per blind signature")
+    a, b, k = b"".join(c1s), b"".join(c2s), b"".join(sks)
+    for v, nb, what in ((a, n * sb, "c1"), (b, n * sb, "c2"), (k, n * 48, "ElGamal secret keys")):
+        need(v, nb, what)
+    out = np.zeros(max(n, 1) * sb, dtype=np.uint8)
+    keep = [buf(v) for v in (a, b, k)]
+    check(lib.cc_unblind_batch(ctx.h, n, keep[0][0], keep[1][0], keep[2][0], ctypes.c_void_p(out.ctypes.data)),
+          "cc_unblind_batch")
+    raw = out.tobytes()
+    return [raw[i * sb:(i + 1) * sb] for i in range(n)]

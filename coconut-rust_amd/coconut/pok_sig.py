@@ -1,4 +1,4 @@
-"""PoKOfSignatureProof::verify — host mirror of the ps_sig 0.1.2 API [EXT] the reference exercises
+"""PoKOfSignature::init / gen_proof and PoKOfSignatureProof::verify — host mirror of the ps_sig 0.1.2 API [EXT] the reference exercises
 in src/pok_sig.rs:85-105 (`proof.verify(&ps_verkey, &ps_params, revealed_msgs, &chal)`).
 
 Responses are ordered as ps_sig builds them: [r2 for g~, m_i for each hidden i ascending]
@@ -8,14 +8,15 @@ does not matter (the sum is order-independent), so indices are sorted here.
 from __future__ import annotations
 
 import ctypes
+import secrets
 from dataclasses import dataclass
-from typing import Dict, List, Union
+from typing import Dict, List, Optional, Sequence, Union
 
 import numpy as np
 
 from ._lib import buf, check, lib, need
 from .errors import CoconutError
-from .signature import GT_BYTES, Context, Params, Verkey, fr_bytes
+from .signature import GT_BYTES, R_ORDER, Context, Params, Signature, Verkey, fr_bytes, hash_msg
 
 
 @dataclass
@@ -72,3 +73,130 @@ def pok_verify_batch(ctx: Context, n: int, q: int, revealed_idx, nresp: int, sig
     if want_gt:
         return verdicts[:n], gts[:n * GT_BYTES].tobytes()
     return verdicts[:n]
+
+
+def _fresh_scalars(count: int) -> bytes:
+    """count scalars from the OS generator: 48 random bytes each, reduced mod r (bias < 2^-128)."""
+    return b"".join((int.from_bytes(secrets.token_bytes(48), "big") % R_ORDER).to_bytes(48, "big")
+                    for _ in range(count))
+
+
+def _idx_array(revealed_idx):
+    r = len(revealed_idx)
+    return np.ascontiguousarray(np.asarray(revealed_idx, dtype=np.uint64)) if r else np.zeros(1, np.uint64)
+
+
+def pok_init_batch(ctx: Context, n: int, q: int, revealed_idx, sigma1: bytes, sigma2: bytes, msgs: bytes,
+                   rand: Optional[bytes] = None):
+    """PoKOfSignature::init for n credentials under the context's params and shared verkey
+    (cc_pok_init_batch).  rand: n x (q - r + 3) x 48 B = r1 | r2 | b_0 .. per credential (b_0 blinds r2,
+    b_{1+j} the j-th hidden message, ascending index); None draws it from `secrets`.
+    Returns (sigma'_1, sigma'_2, J, T, rand): four byte strings of n encodings and the randomness
+    gen_proof needs."""
+    r = len(revealed_idx)
+    nresp = q - r + 1
+    sb, ob = ctx.mode.sig_bytes, ctx.mode.other_bytes
+    if rand is None:
+        rand = _fresh_scalars(n * max(nresp + 2, 0))
+    for v, nb, what in ((sigma1, n * sb, "sigma_1"), (sigma2, n * sb, "sigma_2"), (msgs, n * q * 48, "messages"),
+                        (rand, n * (nresp + 2) * 48, "randomness")):
+        need(v, nb, what)
+    idx = _idx_array(revealed_idx)
+    outs = [np.zeros(max(n, 1) * w, dtype=np.uint8) for w in (sb, sb, ob, ob)]
+    keep = [buf(x) for x in (sigma1, sigma2, msgs, rand)]
+    check(lib.cc_pok_init_batch(ctx.h, n, q, r, nresp, keep[0][0], keep[1][0], keep[2][0],
+                                ctypes.c_void_p(idx.ctypes.data), keep[3][0],
+                                *[ctypes.c_void_p(o.ctypes.data) for o in outs]), "cc_pok_init_batch")
+    s1, s2, J, T = (o.tobytes()[:n * w] for o, w in zip(outs, (sb, sb, ob, ob)))
+    return s1, s2, J, T, bytes(rand)
+
+
+def pok_gen_proof_batch(ctx: Context, n: int, q: int, revealed_idx, msgs: bytes, rand: bytes, chal: bytes) -> bytes:
+    """gen_proof for n committed proofs (cc_pok_gen_proof_batch): n x (q - r + 1) responses of 48 B,
+    responses[0] = b_0 - chal r2, responses[1 + j] = b_{1+j} - chal m_hidden_j."""
+    r = len(revealed_idx)
+    nresp = q - r + 1
+    for v, nb, what in ((msgs, n * q * 48, "messages"), (rand, n * (nresp + 2) * 48, "randomness"),
+                        (chal, n * 48, "challenges")):
+        need(v, nb, what)
+    idx = _idx_array(revealed_idx)
+    out = np.zeros(max(n * max(nresp, 0), 1) * 48, dtype=np.uint8)
+    keep = [buf(x) for x in (msgs, rand, chal)]
+    check(lib.cc_pok_gen_proof_batch(ctx.h, n, q, r, nresp, keep[0][0], ctypes.c_void_p(idx.ctypes.data), keep[1][0],
+                                     keep[2][0], ctypes.c_void_p(out.ctypes.data)), "cc_pok_gen_proof_batch")
+    return out.tobytes()[:n * nresp * 48]
+
+
+def pok_to_bytes_batch(ctx: Context, n: int, q: int, revealed_idx, g_tilde: bytes, Y: Sequence[bytes], sigma1: bytes,
+                       sigma2: bytes, J: bytes, T: bytes) -> List[bytes]:
+    """PoKOfSignature::to_bytes per proof: sigma'_1 || sigma'_2 || J || g~ || Y~_hidden.. || T."""
+    sb, ob = ctx.mode.sig_bytes, ctx.mode.other_bytes
+    for v, nb, what in ((sigma1, n * sb, "sigma'_1"), (sigma2, n * sb, "sigma'_2"), (J, n * ob, "J"),
+                        (T, n * ob, "commitment")):
+        need(v, nb, what)
+    hidden = set(int(i) for i in revealed_idx)
+    bases = bytes(g_tilde) + b"".join(bytes(Y[i]) for i in range(q) if i not in hidden)
+    return [sigma1[i * sb:(i + 1) * sb] + sigma2[i * sb:(i + 1) * sb] + J[i * ob:(i + 1) * ob] + bases +
+            T[i * ob:(i + 1) * ob] for i in range(n)]
+
+
+def pok_challenge_batch(ctx: Context, n: int, q: int, revealed_idx, g_tilde: bytes, Y: Sequence[bytes],
+                        sigma1: bytes, sigma2: bytes, J: bytes, T: bytes) -> bytes:
+    """The reference's challenge (src/pok_sig.rs:94: FieldElement::from_msg_hash(&pok.to_bytes())) for n
+    committed proofs: the to_bytes rows through hash_msg on the GPU; n x 48 B."""
+    return b"".join(hash_msg(ctx, pok_to_bytes_batch(ctx, n, q, revealed_idx, g_tilde, Y, sigma1, sigma2, J, T)))
+
+
+@dataclass
+class PoKOfSignature:
+    """ps_sig PoKOfSignature [EXT] (reference src/pok_sig.rs:80-100): the committed state between init
+    and gen_proof."""
+    sigma_1: bytes           # sigma'_1
+    sigma_2: bytes           # sigma'_2
+    J: bytes
+    commitment: bytes        # T
+    bases: List[bytes]       # g~, Y~_i for hidden i ascending
+    revealed: List[int]
+    msgs: bytes              # the q messages (48 B each)
+    rand: bytes              # r1 | r2 | b_0 .. (secret)
+    ctx: Context = None
+
+    @staticmethod
+    def init(sig: Signature, vk: Verkey, params: Params, msgs: Sequence[Union[int, bytes]],
+             blindings: Optional[Sequence[Union[int, bytes]]] = None, revealed=(), ctx: Context = None,
+             rand: Optional[Sequence[Union[int, bytes]]] = None) -> "PoKOfSignature":
+        """blindings: one per hidden message (ascending index), as ps_sig takes them; the rest (r1, r2
+        and r2's blinding) is drawn from `secrets`.  rand = [r1, r2, b_0, b_1 ..] fixes every draw
+        (replaying a recorded proof)."""
+        ctx = ctx or Context.default()
+        q = len(vk.Y_tilde)
+        if len(msgs) != q:
+            raise CoconutError(-1, f"Verkey valid for {q} messages but given {len(msgs)}")
+        idx = sorted(set(int(i) for i in revealed))
+        hidden = q - len(idx)
+        if rand is not None:
+            if len(rand) != hidden + 3:
+                raise CoconutError(-2, f"rand holds {len(rand)} scalars, init draws {hidden + 3}")
+            rb = b"".join(fr_bytes(x) for x in rand)
+        else:
+            if blindings is not None and len(blindings) != hidden:
+                raise CoconutError(-2, f"{len(blindings)} blindings for {hidden} hidden messages")
+            rb = _fresh_scalars(3) + (b"".join(fr_bytes(b) for b in blindings) if blindings is not None
+                                      else _fresh_scalars(hidden))
+        ctx.set_params(params.g_tilde)
+        ctx.set_verkey(vk.X_tilde, vk.Y_tilde)
+        mb = b"".join(fr_bytes(m) for m in msgs)
+        s1, s2, J, T, rb = pok_init_batch(ctx, 1, q, idx, sig.sigma_1, sig.sigma_2, mb, rb)
+        rev = set(idx)
+        bases = [bytes(params.g_tilde)] + [bytes(vk.Y_tilde[i]) for i in range(q) if i not in rev]
+        return PoKOfSignature(s1, s2, J, T, bases, idx, mb, rb, ctx)
+
+    def to_bytes(self) -> bytes:
+        return self.sigma_1 + self.sigma_2 + self.J + b"".join(self.bases) + self.commitment
+
+    def gen_proof(self, chal: Union[int, bytes]) -> PoKOfSignatureProof:
+        ctx = self.ctx or Context.default()
+        q = len(self.msgs) // 48
+        resp = pok_gen_proof_batch(ctx, 1, q, self.revealed, self.msgs, self.rand, fr_bytes(chal))
+        return PoKOfSignatureProof(self.sigma_1, self.sigma_2, self.J, self.commitment,
+                                   [resp[k:k + 48] for k in range(0, len(resp), 48)])

@@ -105,6 +105,16 @@ int cck_prep_pok_wide(int mode, size_t n, int q, int r, const uint8_t* d_s1, con
                  const uint8_t* d_T, const uint8_t* d_resp, const uint8_t* d_chal, const uint8_t* d_rev_msgs,
                  const uint32_t* d_rev_idx, const uint32_t* d_Xaff, uint32_t Xinf, const uint32_t* d_table, int wbits,
                  const uint32_t* d_binf, uint32_t* d_prep, uint32_t* d_flags, uint32_t* d_jtab, hipStream_t st);
+size_t cck_sigma_prime_words(int mode, size_t n);
+int cck_sigma_prime(int mode, size_t n, size_t rstride, const uint8_t* d_s1, const uint8_t* d_s2, const uint8_t* d_rnd,
+                    uint32_t* d_scratch, uint8_t* d_o1, uint8_t* d_o2, hipStream_t st);
+int cck_pok_commit(int mode, size_t n, int q, int r, const uint8_t* d_msgs, const uint8_t* d_rnd,
+                   const uint32_t* d_rev_idx, const uint32_t* d_table, int wbits, const uint32_t* d_binf, uint8_t* d_J,
+                   uint8_t* d_T, hipStream_t st);
+int cck_pok_responses(size_t n, int q, int r, const uint8_t* d_msgs, const uint8_t* d_rnd, const uint8_t* d_chal,
+                      const uint32_t* d_rev_idx, uint8_t* d_out, hipStream_t st);
+int cck_unblind_assemble(int group, size_t n, const uint8_t* d_c1, const uint8_t* d_c2, const uint8_t* d_sk,
+                         uint8_t* d_pts, uint32_t* d_sc, hipStream_t st);
 }
 
 namespace {
@@ -257,6 +267,7 @@ struct cc_ctx {
     // identity flags
     DevBuf rlc_pts, rlc_dig, rlc_work, rlc_pw, rlc_finf;
     DevBuf pok_idx;  // revealed indices of the last PoK batch
+    DevBuf prove_idx, prove_scratch;  // holder side (pok_prove.hip): revealed indices, sigma' entry tables
     int n_simd = 0;  // SIMDs of the device (4 a CU), read once (pok_rlc_twin)
     // issuer table (cc_set_issuers): sorted ids, decoded verkeys, per-base 8-bit window tables
     size_t iss_n = 0, iss_q = 0;
@@ -459,7 +470,8 @@ cc_status cc_ctx_destroy(cc_ctx* c) {
                       &c->fbuf, &c->scratch, &c->verdicts, &c->gt, &c->vkb, &c->lag, &c->wide_prep, &c->wide_flags, &c->wide_f,
                       &c->rlc_key, &c->rlc_any, &c->rlc_part, &c->rlc_flag, &c->rlc_accept, &c->fin_f, &c->fin_scratch, &c->fin_prep, &c->fin_flags2, &c->fin_part, &c->pok_idx, &c->rlc_gath,
                       &c->rlc_pts, &c->rlc_dig, &c->rlc_work, &c->rlc_pw, &c->rlc_finf,
-                      &c->iss_ids, &c->iss_aff, &c->iss_inf, &c->iss_table, &c->agg_scratch, &c->dev_err};
+                      &c->iss_ids, &c->iss_aff, &c->iss_inf, &c->iss_table, &c->agg_scratch, &c->dev_err,
+                      &c->prove_idx, &c->prove_scratch};
     for (auto* b : bufs) b->release();
     for (auto& b : c->in_aux) b.release();
     for (auto& e : c->ev) if (e) (void)hipEventDestroy(e);
@@ -1995,6 +2007,199 @@ cc_status cc_pok_verify_batch_rlc(cc_ctx* c, size_t n, size_t q, size_t r, size_
     return pok_host(c, n, q, r, nresp, s1, s2, J, T, resp, chal, rev_idx, rev_msgs, verdicts, nullptr, 1);
 }
 
+
+// ---------------------------------------------------------------- holder side (pok_prove.hip)
+// the checks cc_pok_verify_batch_device makes, in its order; with_vk: PoKOfSignature::init needs the
+// verkey's tables, gen_proof only the shape
+static cc_status prove_checks(const cc_ctx* c, bool with_vk, size_t q, size_t r, size_t nresp, const uint64_t* rev_idx,
+                              std::vector<uint32_t>& idx) {
+    if (with_vk) {
+        if (!c->have_params || !c->have_vk) return CC_ERR_STATE;
+        if (q != c->q) return CC_ERR_LEN;
+    } else if (q > kMaxQ) {
+        return CC_ERR_DECODE;
+    }
+    // more than q indices hold one >= q or a repeated one among the first q + 1
+    cc_status s = check_revealed(q, std::min(r, q + 1), rev_idx, idx);
+    if (s) return s;
+    if (nresp != q - r + 1) return CC_ERR_BASES_EXPS;
+    return CC_OK;
+}
+
+static cc_status launch_pok_init(cc_ctx* c, size_t n, size_t q, size_t r, const uint8_t* d_s1, const uint8_t* d_s2,
+                                 const uint8_t* d_msgs, const uint32_t* d_idx, const uint8_t* d_rand, uint8_t* d_o1,
+                                 uint8_t* d_o2, uint8_t* d_J, uint8_t* d_T, hipStream_t st) {
+    KCK(cck_sigma_prime(c->mode, n, q - r + 3, d_s1, d_s2, d_rand, c->prove_scratch.as<uint32_t>(), d_o1, d_o2, st));
+    KCK(cck_pok_commit(c->mode, n, (int)q, (int)r, d_msgs, d_rand, d_idx, c->table.as<uint32_t>(), c->wbits,
+                       c->table_inf.as<uint32_t>(), d_J, d_T, st));
+    return CC_OK;
+}
+
+cc_status cc_pok_init_batch_device(cc_ctx* c, size_t n, size_t q, size_t r, size_t nresp, const uint8_t* d_s1,
+                                   const uint8_t* d_s2, const uint8_t* d_msgs, const uint64_t* rev_idx,
+                                   const uint8_t* d_rand, uint8_t* d_o1, uint8_t* d_o2, uint8_t* d_J, uint8_t* d_T,
+                                   void* stream) {
+    c = primary(c);  // a device set forwards to its first device
+    if (!c || (r && !rev_idx) || (n && (!d_s1 || !d_s2 || !d_rand || !d_o1 || !d_o2 || !d_J || !d_T || (q && !d_msgs))))
+        return CC_ERR_DECODE;
+    std::vector<uint32_t> idx;
+    cc_status s = prove_checks(c, true, q, r, nresp, rev_idx, idx);
+    if (s) return s;
+    if (n > kMaxBatch) return CC_ERR_DECODE;
+    if (!n) return CC_OK;
+    HIPCK(hipSetDevice(c->device));
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    StreamOrder order(c, st);
+    if (c->prove_idx.ensure(idx.size() * 4) || c->prove_scratch.ensure(cck_sigma_prime_words(c->mode, n) * 4))
+        return CC_ERR_HIP;
+    HIPCK(hipMemcpyAsync(c->prove_idx.p, idx.data(), idx.size() * 4, hipMemcpyHostToDevice, st));
+    return launch_pok_init(c, n, q, r, d_s1, d_s2, d_msgs, c->prove_idx.as<uint32_t>(), d_rand, d_o1, d_o2, d_J, d_T, st);
+}
+
+cc_status cc_pok_init_batch(cc_ctx* c, size_t n, size_t q, size_t r, size_t nresp, const uint8_t* s1, const uint8_t* s2,
+                            const uint8_t* msgs, const uint64_t* rev_idx, const uint8_t* rand, uint8_t* o1, uint8_t* o2,
+                            uint8_t* oJ, uint8_t* oT) {
+    c = primary(c);  // a device set forwards to its first device
+    if (!c || (r && !rev_idx) || (n && (!s1 || !s2 || !rand || !o1 || !o2 || !oJ || !oT || (q && !msgs))))
+        return CC_ERR_DECODE;
+    std::vector<uint32_t> idx;
+    cc_status s = prove_checks(c, true, q, r, nresp, rev_idx, idx);
+    if (s) return s;
+    if (n > kMaxBatch) return CC_ERR_DECODE;
+    if (!n) return CC_OK;
+    HIPCK(hipSetDevice(c->device));
+    drain_slots(c);  // concurrent device batches (cc_set_concurrency) before the workspaces are resized
+    const size_t sb = (size_t)sig_bytes(c->mode), ob = (size_t)oth_bytes(c->mode), rb = n * (nresp + 2) * 48;
+    const size_t scr = cck_sigma_prime_words(c->mode, n) * 4;
+    hipStream_t st = c->stream;
+    DevBuf& dR = c->in_aux[0];
+    DevBuf& d1 = c->in_aux[1];
+    DevBuf& d2 = c->in_aux[2];
+    DevBuf& dJ = c->in_aux[3];
+    DevBuf& dT = c->in_aux[4];
+    if (c->in_s1.ensure(n * sb) || c->in_s2.ensure(n * sb) || c->in_msgs.ensure(n * q * 48 + 16) || dR.ensure(rb) ||
+        d1.ensure(n * sb) || d2.ensure(n * sb) || dJ.ensure(n * ob) || dT.ensure(n * ob) ||
+        c->prove_idx.ensure(idx.size() * 4) || c->prove_scratch.ensure(scr))
+        return CC_ERR_HIP;
+    auto run = [&]() -> cc_status {
+        HIPCK(hipMemcpyAsync(c->in_s1.p, s1, n * sb, hipMemcpyHostToDevice, st));
+        HIPCK(hipMemcpyAsync(c->in_s2.p, s2, n * sb, hipMemcpyHostToDevice, st));
+        if (q) HIPCK(hipMemcpyAsync(c->in_msgs.p, msgs, n * q * 48, hipMemcpyHostToDevice, st));
+        HIPCK(hipMemcpyAsync(dR.p, rand, rb, hipMemcpyHostToDevice, st));
+        HIPCK(hipMemcpyAsync(c->prove_idx.p, idx.data(), idx.size() * 4, hipMemcpyHostToDevice, st));
+        cc_status e = launch_pok_init(c, n, q, r, c->in_s1.as<uint8_t>(), c->in_s2.as<uint8_t>(), c->in_msgs.as<uint8_t>(),
+                                      c->prove_idx.as<uint32_t>(), dR.as<uint8_t>(), d1.as<uint8_t>(), d2.as<uint8_t>(),
+                                      dJ.as<uint8_t>(), dT.as<uint8_t>(), st);
+        if (e) return e;
+        HIPCK(hipMemcpyAsync(o1, d1.p, n * sb, hipMemcpyDeviceToHost, st));
+        HIPCK(hipMemcpyAsync(o2, d2.p, n * sb, hipMemcpyDeviceToHost, st));
+        HIPCK(hipMemcpyAsync(oJ, dJ.p, n * ob, hipMemcpyDeviceToHost, st));
+        HIPCK(hipMemcpyAsync(oT, dT.p, n * ob, hipMemcpyDeviceToHost, st));
+        return CC_OK;
+    };
+    s = run();
+    // the device copies of the secrets (r1, r2, the blindings; the digits of r1 and r1 r2) are zeroed
+    const bool wiped = hipMemsetAsync(dR.p, 0, rb, st) == hipSuccess &&
+                       hipMemsetAsync(c->prove_scratch.p, 0, scr, st) == hipSuccess;
+    if (hipStreamSynchronize(st) != hipSuccess || !wiped) return s ? s : CC_ERR_HIP;
+    return s;
+}
+
+cc_status cc_pok_gen_proof_batch_device(cc_ctx* c, size_t n, size_t q, size_t r, size_t nresp, const uint8_t* d_msgs,
+                                        const uint64_t* rev_idx, const uint8_t* d_rand, const uint8_t* d_chal,
+                                        uint8_t* d_out, void* stream) {
+    c = primary(c);  // a device set forwards to its first device
+    if (!c || (r && !rev_idx) || (n && (!d_rand || !d_chal || !d_out || (q && !d_msgs)))) return CC_ERR_DECODE;
+    std::vector<uint32_t> idx;
+    cc_status s = prove_checks(c, false, q, r, nresp, rev_idx, idx);
+    if (s) return s;
+    if (n > kMaxBatch) return CC_ERR_DECODE;
+    if (!n) return CC_OK;
+    HIPCK(hipSetDevice(c->device));
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    StreamOrder order(c, st);
+    if (c->prove_idx.ensure(idx.size() * 4)) return CC_ERR_HIP;
+    HIPCK(hipMemcpyAsync(c->prove_idx.p, idx.data(), idx.size() * 4, hipMemcpyHostToDevice, st));
+    KCK(cck_pok_responses(n, (int)q, (int)r, d_msgs, d_rand, d_chal, c->prove_idx.as<uint32_t>(), d_out, st));
+    return CC_OK;
+}
+
+cc_status cc_pok_gen_proof_batch(cc_ctx* c, size_t n, size_t q, size_t r, size_t nresp, const uint8_t* msgs,
+                                 const uint64_t* rev_idx, const uint8_t* rand, const uint8_t* chal, uint8_t* out) {
+    c = primary(c);  // a device set forwards to its first device
+    if (!c || (r && !rev_idx) || (n && (!rand || !chal || !out || (q && !msgs)))) return CC_ERR_DECODE;
+    std::vector<uint32_t> idx;
+    cc_status s = prove_checks(c, false, q, r, nresp, rev_idx, idx);
+    if (s) return s;
+    if (n > kMaxBatch) return CC_ERR_DECODE;
+    if (!n) return CC_OK;
+    HIPCK(hipSetDevice(c->device));
+    drain_slots(c);  // concurrent device batches (cc_set_concurrency) before the workspaces are resized
+    const size_t rb = n * (nresp + 2) * 48;
+    hipStream_t st = c->stream;
+    DevBuf& dR = c->in_aux[0];
+    DevBuf& dC = c->in_aux[1];
+    DevBuf& dO = c->in_aux[2];
+    if (c->in_msgs.ensure(n * q * 48 + 16) || dR.ensure(rb) || dC.ensure(n * 48) || dO.ensure(n * nresp * 48) ||
+        c->prove_idx.ensure(idx.size() * 4))
+        return CC_ERR_HIP;
+    auto run = [&]() -> cc_status {
+        if (q) HIPCK(hipMemcpyAsync(c->in_msgs.p, msgs, n * q * 48, hipMemcpyHostToDevice, st));
+        HIPCK(hipMemcpyAsync(dR.p, rand, rb, hipMemcpyHostToDevice, st));
+        HIPCK(hipMemcpyAsync(dC.p, chal, n * 48, hipMemcpyHostToDevice, st));
+        HIPCK(hipMemcpyAsync(c->prove_idx.p, idx.data(), idx.size() * 4, hipMemcpyHostToDevice, st));
+        KCK(cck_pok_responses(n, (int)q, (int)r, c->in_msgs.as<uint8_t>(), dR.as<uint8_t>(), dC.as<uint8_t>(),
+                              c->prove_idx.as<uint32_t>(), dO.as<uint8_t>(), st));
+        HIPCK(hipMemcpyAsync(out, dO.p, n * nresp * 48, hipMemcpyDeviceToHost, st));
+        return CC_OK;
+    };
+    s = run();
+    const bool wiped = hipMemsetAsync(dR.p, 0, rb, st) == hipSuccess;  // r2 and the blindings
+    if (hipStreamSynchronize(st) != hipSuccess || !wiped) return s ? s : CC_ERR_HIP;
+    return s;
+}
+
+cc_status cc_unblind_batch(cc_ctx* c, size_t n, const uint8_t* c1, const uint8_t* c2, const uint8_t* sk,
+                           uint8_t* out_sigma2) {
+    c = primary(c);  // a device set forwards to its first device
+    if (!c || (n && (!c1 || !c2 || !sk || !out_sigma2))) return CC_ERR_DECODE;
+    if (n > kMaxBatch) return CC_ERR_DECODE;
+    if (!n) return CC_OK;
+    HIPCK(hipSetDevice(c->device));
+    drain_slots(c);  // concurrent device batches (cc_set_concurrency) before the workspaces are resized
+    const size_t sb = (size_t)sig_bytes(c->mode);
+    const int sg = sig_group(c->mode);
+    const size_t scr = n * cck_straus_words(sg, 2) * 4;
+    hipStream_t st = c->stream;
+    DevBuf& dK = c->in_aux[0];
+    DevBuf& dP = c->in_aux[1];
+    DevBuf& dS = c->in_aux[2];
+    DevBuf& dO = c->in_aux[3];
+    if (c->in_s1.ensure(n * sb) || c->in_s2.ensure(n * sb) || dK.ensure(n * 48) || dP.ensure(n * 2 * sb) ||
+        dS.ensure(n * 64) || dO.ensure(n * sb))
+        return CC_ERR_HIP;
+    cc_status s = agg_scratch(c, sg, n, 2);
+    if (s) return s;
+    auto run = [&]() -> cc_status {
+        HIPCK(hipMemcpyAsync(c->in_s1.p, c1, n * sb, hipMemcpyHostToDevice, st));
+        HIPCK(hipMemcpyAsync(c->in_s2.p, c2, n * sb, hipMemcpyHostToDevice, st));
+        HIPCK(hipMemcpyAsync(dK.p, sk, n * 48, hipMemcpyHostToDevice, st));
+        KCK(cck_unblind_assemble(sg, n, c->in_s1.as<uint8_t>(), c->in_s2.as<uint8_t>(), dK.as<uint8_t>(),
+                                 dP.as<uint8_t>(), dS.as<uint32_t>(), st));
+        // sigma_2 = c2 + (-sk) c1: one t = 2 Straus task a row (as cc_blind_sign_batch drives it)
+        KCK(cck_msm_straus(sg, n, 2, dP.as<uint8_t>(), 2 * sb, 0, sb, dS.as<uint32_t>(), 1,
+                           c->agg_scratch.as<uint32_t>(), dO.as<uint8_t>(), st));
+        HIPCK(hipMemcpyAsync(out_sigma2, dO.p, n * sb, hipMemcpyDeviceToHost, st));
+        return CC_OK;
+    };
+    s = run();
+    // the device copies of sk, of -sk and of its digits (the Straus scratch) are zeroed
+    const bool wiped = hipMemsetAsync(dK.p, 0, n * 48, st) == hipSuccess &&
+                       hipMemsetAsync(dS.p, 0, n * 64, st) == hipSuccess &&
+                       hipMemsetAsync(c->agg_scratch.p, 0, scr, st) == hipSuccess;
+    if (hipStreamSynchronize(st) != hipSuccess || !wiped) return s ? s : CC_ERR_HIP;
+    return s;
+}
 
 // ---------------------------------------------------------------- device sets + RCCL
 cc_status cc_ctx_create_multi(uint64_t device_mask, cc_group_mode mode, cc_ctx** out) {

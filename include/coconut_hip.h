@@ -13,6 +13,10 @@
  *        replaces  Verkey::aggregate              src/signature.rs:483-526
  *   cc_pok_verify_batch
  *        replaces  ps_sig PoKOfSignatureProof::verify [EXT], called at src/pok_sig.rs:103-105
+ *   cc_pok_init_batch / cc_pok_gen_proof_batch
+ *        replaces  ps_sig PoKOfSignature::init / gen_proof [EXT], called at src/pok_sig.rs:80-100
+ *   cc_unblind_batch
+ *        replaces  BlindSignature::unblind        src/signature.rs:436-443
  *   cc_set_params / cc_set_verkey
  *        the Params (src/signature.rs:13-17, only g_tilde is read by verify) and Verkey
  *        (src/signature.rs:46-49) a batch is checked against
@@ -249,6 +253,54 @@ cc_status cc_pok_verify_batch_device(cc_ctx* ctx, size_t n, size_t q, size_t r, 
                                      const uint8_t* d_responses, const uint8_t* d_chal, const uint64_t* revealed_idx,
                                      const uint8_t* d_revealed_msgs, uint8_t* d_verdicts, uint8_t* d_gt_or_null,
                                      void* stream);
+
+/* Holder side: ps_sig PoKOfSignature::init / gen_proof [EXT] (reference src/pok_sig.rs:80-100) and
+ * BlindSignature::unblind (src/signature.rs:436-443), what cc_pok_verify_batch consumes.
+ *
+ * PoKOfSignature::init for n credentials under the shared verkey and params.
+ *   sigma1, sigma2 : n x SignatureGroup      msgs : n x q x 48
+ *   revealed_idx   : r indices (host array, rules of cc_pok_verify_batch)
+ *   rand           : n x (nresp + 2) x 48 = r1 | r2 | b_0 .. b_{nresp-1}   (caller's randomness)
+ *   out: sigma'_1 = r1 s1, sigma'_2 = r1 (s2 + r2 s1)      (n x SignatureGroup each)
+ *        J = r2 g~ + sum_hidden m_i Y~_i,  T = b_0 g~ + sum_hidden b_j Y~_i   (n x OtherGroup each)
+ *   bases and responses ordered [g~, Y~_i for hidden i ascending], as cc_pok_verify_batch reads them
+ * Checks, in cc_pok_verify_batch_device's order and before the n = 0 shortcut: NULL context, or a NULL
+ * buffer with n > 0, or NULL revealed_idx with r > 0: CC_ERR_DECODE; no params / verkey: CC_ERR_STATE
+ * (init only; gen_proof and unblind need neither); q != the verkey's q: CC_ERR_LEN (gen_proof: q >
+ * CC_MAX_Q is CC_ERR_DECODE); an index >= q: CC_ERR_LEN, a repeated index: CC_ERR_DECODE; nresp !=
+ * q - r + 1: CC_ERR_BASES_EXPS; n > CC_MAX_BATCH: CC_ERR_DECODE.
+ * Scalars are reduced mod r, a bad prefix or an off-curve point decodes to the identity, an identity
+ * result (r1 = 0, sigma_2 = -r2 sigma_1, all blindings 0) is written as the identity encoding; nothing
+ * is rejected that ps_sig would not reject.
+ * The *_device forms take device pointers (revealed_idx stays a host array), are asynchronous on
+ * `stream` (NULL: the context stream) and take no concurrency slot: they first wait for the slots'
+ * batches.  A device set forwards to its first device.
+ * Secrets: the host forms copy rand (r1, r2, the blindings) and sk to the device and build the digits of
+ * r1, r1 r2 and -sk in device scratch; they overwrite those device copies with zeros before
+ * returning.  The *_device forms read the caller's buffers in place; their scratch (the digits of r1
+ * and r1 r2) stays until the next call overwrites it or the context is destroyed. */
+cc_status cc_pok_init_batch(cc_ctx* ctx, size_t n, size_t q, size_t r, size_t nresp, const uint8_t* sigma1,
+                            const uint8_t* sigma2, const uint8_t* msgs, const uint64_t* revealed_idx,
+                            const uint8_t* rand, uint8_t* out_sigma1, uint8_t* out_sigma2, uint8_t* out_J,
+                            uint8_t* out_T);
+cc_status cc_pok_init_batch_device(cc_ctx* ctx, size_t n, size_t q, size_t r, size_t nresp, const uint8_t* d_sigma1,
+                                   const uint8_t* d_sigma2, const uint8_t* d_msgs, const uint64_t* revealed_idx,
+                                   const uint8_t* d_rand, uint8_t* d_out_sigma1, uint8_t* d_out_sigma2,
+                                   uint8_t* d_out_J, uint8_t* d_out_T, void* stream);
+
+/* gen_proof: responses[0] = b_0 - chal r2, responses[1 + j] = b_{1+j} - chal m_hidden_j  (mod r);
+ * msgs, rand as cc_pok_init_batch, chal n x 48, out_responses n x nresp x 48. */
+cc_status cc_pok_gen_proof_batch(cc_ctx* ctx, size_t n, size_t q, size_t r, size_t nresp, const uint8_t* msgs,
+                                 const uint64_t* revealed_idx, const uint8_t* rand, const uint8_t* chal,
+                                 uint8_t* out_responses);
+cc_status cc_pok_gen_proof_batch_device(cc_ctx* ctx, size_t n, size_t q, size_t r, size_t nresp,
+                                        const uint8_t* d_msgs, const uint64_t* revealed_idx, const uint8_t* d_rand,
+                                        const uint8_t* d_chal, uint8_t* d_out_responses, void* stream);
+
+/* BlindSignature::unblind: sigma_2 = c2 - sk c1, one ElGamal key per row (c1, c2: n x SignatureGroup,
+ * sk: n x 48); sigma_1 is the blind signature's h.  An identity c1 or sk = 0 gives c2 back. */
+cc_status cc_unblind_batch(cc_ctx* ctx, size_t n, const uint8_t* c1, const uint8_t* c2, const uint8_t* sk,
+                           uint8_t* out_sigma2);
 
 /* RLC batch mode for PoKOfSignatureProof::verify (shared verkey).  The proof's pairing equation
  * e(sigma'_1, J') * e(-sigma'_2, g~) == 1, J' = X~ + J + sum_revealed m_i Y~_i, has the shape of

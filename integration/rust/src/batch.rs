@@ -192,5 +192,75 @@ pub fn pok_verify_batch(proofs: &[(Vec<u8>, Vec<u8>, Vec<u8>, Vec<u8>, Vec<Field
     v.into_iter().map(|b| b == 1).collect()
 }
 
+/// One holder-side proof as its serialized parts: (sigma'_1, sigma'_2, J, T, responses), the tuple
+/// `pok_verify_batch` takes.
+pub type ProofParts = (Vec<u8>, Vec<u8>, Vec<u8>, Vec<u8>, Vec<FieldElement>);
+
+/// PoKOfSignature::init + gen_proof (ps_sig, called at pok_sig.rs:80-100) for n credentials under one
+/// verkey: fresh r1, r2 and blindings per credential (FieldElement::random), both sigma' and J, T on the
+/// GPU, the challenge as the reference derives it (pok_sig.rs:94: from_msg_hash of to_bytes), the
+/// responses on the GPU.  Returns every proof's parts and its challenge.
+pub fn pok_prove_batch(sigs: &[Signature], messages: &[Vec<FieldElement>], revealed_idx: &[u64], vk: &Verkey,
+                       params: &Params, ctx: &HipCtx) -> Vec<(ProofParts, FieldElement)> {
+    let (n, q, r) = (sigs.len(), vk.Y_tilde.len(), revealed_idx.len());
+    if n == 0 { return Vec::new(); }
+    assert_eq!(messages.len(), n, "one message vector per signature");  // len-guard
+    assert!(messages.iter().all(|m| m.len() == q), "Verkey valid for {} messages", q);  // len-guard
+    assert!(r <= q && revealed_idx.iter().all(|&i| (i as usize) < q), "revealed indices below q");  // len-guard
+    let nresp = q - r + 1;
+    let (sb, ob) = (ctx.sig_bytes(), ctx.oth_bytes());
+    let s1: Vec<u8> = sigs.iter().flat_map(|s| s.sigma_1.to_bytes()).collect();
+    let s2: Vec<u8> = sigs.iter().flat_map(|s| s.sigma_2.to_bytes()).collect();
+    let m: Vec<u8> = messages.iter().flatten().flat_map(|f| f.to_bytes()).collect();
+    let rand: Vec<u8> = (0..n * (nresp + 2)).flat_map(|_| FieldElement::random().to_bytes()).collect();
+    assert!(s1.len() == n * sb && s2.len() == n * sb, "signature encodings");  // len-guard
+    assert!(m.len() == n * q * 48 && rand.len() == n * (nresp + 2) * 48, "scalar encodings");  // len-guard
+    ctx.set_params(&params.g_tilde.to_bytes());
+    ctx.set_verkey(&vk.X_tilde.to_bytes(), &vk.Y_tilde.iter().flat_map(|y| y.to_bytes()).collect::<Vec<u8>>(), q);
+    let (mut o1, mut o2) = (vec![0u8; n * sb], vec![0u8; n * sb]);
+    let (mut oj, mut ot) = (vec![0u8; n * ob], vec![0u8; n * ob]);
+    ctx.check(unsafe { cc_pok_init_batch(ctx.raw, n, q, r, nresp, s1.as_ptr(), s2.as_ptr(), m.as_ptr(),
+                                         revealed_idx.as_ptr(), rand.as_ptr(), o1.as_mut_ptr(), o2.as_mut_ptr(),
+                                         oj.as_mut_ptr(), ot.as_mut_ptr()) });
+    // to_bytes: sigma'_1 || sigma'_2 || J || g~ || Y~_hidden.. || T
+    let mut bases = params.g_tilde.to_bytes();
+    for i in 0..q {
+        if !revealed_idx.contains(&(i as u64)) { bases.extend_from_slice(&vk.Y_tilde[i].to_bytes()); }
+    }
+    let chals: Vec<FieldElement> = (0..n).map(|i| {
+        let row = [&o1[i * sb..(i + 1) * sb], &o2[i * sb..(i + 1) * sb], &oj[i * ob..(i + 1) * ob], &bases[..],
+                   &ot[i * ob..(i + 1) * ob]].concat();
+        FieldElement::from_msg_hash(&row)
+    }).collect();
+    let ch: Vec<u8> = chals.iter().flat_map(|c| c.to_bytes()).collect();
+    assert_eq!(ch.len(), n * 48, "challenge encodings");  // len-guard
+    let mut resp = vec![0u8; n * nresp * 48];
+    ctx.check(unsafe { cc_pok_gen_proof_batch(ctx.raw, n, q, r, nresp, m.as_ptr(), revealed_idx.as_ptr(),
+                                              rand.as_ptr(), ch.as_ptr(), resp.as_mut_ptr()) });
+    chals.into_iter().enumerate().map(|(i, c)| {
+        let rs = (0..nresp).map(|k| FieldElement::from_bytes(&resp[(i * nresp + k) * 48..(i * nresp + k + 1) * 48]).unwrap())
+            .collect();
+        ((o1[i * sb..(i + 1) * sb].to_vec(), o2[i * sb..(i + 1) * sb].to_vec(), oj[i * ob..(i + 1) * ob].to_vec(),
+          ot[i * ob..(i + 1) * ob].to_vec(), rs), c)
+    }).collect()
+}
+
+/// BlindSignature::unblind (signature.rs:436-443) for n blind signatures, each with its own ElGamal
+/// secret key: Signature { sigma_1: h, sigma_2: c~2 - sk c~1 }.
+pub fn unblind_batch(blind: &[BlindSignature], sks: &[FieldElement], ctx: &HipCtx) -> Vec<Signature> {
+    let n = blind.len();
+    if n == 0 { return Vec::new(); }
+    assert_eq!(sks.len(), n, "one ElGamal secret key per blind signature");  // len-guard
+    let sb = ctx.sig_bytes();
+    let c1: Vec<u8> = blind.iter().flat_map(|b| b.blinded.0.to_bytes()).collect();
+    let c2: Vec<u8> = blind.iter().flat_map(|b| b.blinded.1.to_bytes()).collect();
+    let sk: Vec<u8> = sks.iter().flat_map(|s| s.to_bytes()).collect();
+    assert!(c1.len() == n * sb && c2.len() == n * sb && sk.len() == n * 48, "ciphertext and key encodings");  // len-guard
+    let mut out = vec![0u8; n * sb];
+    ctx.check(unsafe { cc_unblind_batch(ctx.raw, n, c1.as_ptr(), c2.as_ptr(), sk.as_ptr(), out.as_mut_ptr()) });
+    blind.iter().enumerate().map(|(i, b)| Signature {
+        sigma_1: b.h.clone(), sigma_2: SignatureGroup::from_bytes(&out[i * sb..(i + 1) * sb]).unwrap() }).collect()
+}
+
 #[allow(dead_code)]
 const _MODE_TYPE: c_int = CC_SIG_G2;

@@ -76,6 +76,22 @@ extern "C" {
                                       d_responses: *const u8, d_chal: *const u8, revealed_idx: *const u64,
                                       d_revealed_msgs: *const u8, d_verdicts: *mut u8, d_gt: *mut u8,
                                       stream: *mut c_void) -> c_int;
+    // holder side: PoKOfSignature::init / gen_proof (pok_sig.rs:80-100), BlindSignature::unblind (signature.rs:436-443)
+    pub fn cc_pok_init_batch(ctx: *mut CcCtx, n: usize, q: usize, r: usize, nresp: usize, sigma1: *const u8,
+                             sigma2: *const u8, msgs: *const u8, revealed_idx: *const u64, rand: *const u8,
+                             out_sigma1: *mut u8, out_sigma2: *mut u8, out_j: *mut u8, out_t: *mut u8) -> c_int;
+    pub fn cc_pok_init_batch_device(ctx: *mut CcCtx, n: usize, q: usize, r: usize, nresp: usize, d_sigma1: *const u8,
+                                    d_sigma2: *const u8, d_msgs: *const u8, revealed_idx: *const u64,
+                                    d_rand: *const u8, d_out_sigma1: *mut u8, d_out_sigma2: *mut u8,
+                                    d_out_j: *mut u8, d_out_t: *mut u8, stream: *mut c_void) -> c_int;
+    pub fn cc_pok_gen_proof_batch(ctx: *mut CcCtx, n: usize, q: usize, r: usize, nresp: usize, msgs: *const u8,
+                                  revealed_idx: *const u64, rand: *const u8, chal: *const u8,
+                                  out_responses: *mut u8) -> c_int;
+    pub fn cc_pok_gen_proof_batch_device(ctx: *mut CcCtx, n: usize, q: usize, r: usize, nresp: usize,
+                                         d_msgs: *const u8, revealed_idx: *const u64, d_rand: *const u8,
+                                         d_chal: *const u8, d_out_responses: *mut u8, stream: *mut c_void) -> c_int;
+    pub fn cc_unblind_batch(ctx: *mut CcCtx, n: usize, c1: *const u8, c2: *const u8, sk: *const u8,
+                            out_sigma2: *mut u8) -> c_int;
     // RLC batch mode for PoK proofs: the partial (finished by cc_rlc_finish_device) and the host form
     pub fn cc_pok_rlc_partial_device(ctx: *mut CcCtx, n: usize, q: usize, r: usize, nresp: usize, base_index: u64,
                                      seed32: *const u8, d_sigma1: *const u8, d_sigma2: *const u8, d_j: *const u8,
