@@ -2,8 +2,8 @@
 
 Mirrors 3for/coconut-rust (`/root/reference/src/lib.rs:26-31` module list) for the hot path only:
 `signature` (Signature::verify / aggregate, Verkey::aggregate + batch entry points), `pok_sig`
-(PoKOfSignature::init / gen_proof, PoKOfSignatureProof::verify), `issuance` (issuer-side batches and
-BlindSignature::unblind), `errors`.  Every computation runs in libcoconut_hip.so on the GPU; importing
+(PoKOfSignature::init / gen_proof, PoKOfSignatureProof::verify), `issuance` (issuer-side batches, the
+holder's SignatureRequest::new, SignatureRequestPoK and BlindSignature::unblind), `errors`.  Every computation runs in libcoconut_hip.so on the GPU; importing
 this package on a machine without the built library raises immediately.
 """
 from .errors import CoconutError, CoconutErrorKind  # noqa: F401
@@ -14,4 +14,7 @@ from .signature import (GroupMode, Params, Verkey, Signature, Context, verify_ba
 from .pok_sig import (PoKOfSignature, PoKOfSignatureProof, pok_verify_batch, pok_init_batch,  # noqa: F401
                       pok_gen_proof_batch, pok_challenge_batch, pok_to_bytes_batch)
 from .dist import DeviceEngine, PokDeviceEngine  # noqa: F401
-from .issuance import blind_sign_batch, sigreq_verify_batch, vss_verify_batch, unblind_batch  # noqa: F401
+from .issuance import (blind_sign_batch, sigreq_verify_batch, vss_verify_batch, unblind_batch,  # noqa: F401
+                       SignatureRequest, SignatureRequestPoK, sigreq_new_batch, sigreq_pok_init_batch,
+                       sigreq_pok_gen_proof_batch, sigreq_pok_to_bytes_batch, sigreq_challenge_batch,
+                       sigreq_proof_bytes)

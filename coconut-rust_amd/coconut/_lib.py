@@ -72,6 +72,13 @@ _SIGS = {
     "cc_blind_sign_batch": (c_int, [c_p, c_sz, c_sz, c_sz, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
     "cc_sigreq_proof_bytes": (c_sz, [c_p, c_sz]),
     "cc_sigreq_verify_batch": (c_int, [c_p, c_sz, c_sz, c_sz, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "cc_set_request_params": (c_int, [c_p, c_sz, c_p, c_p, c_int]),
+    "cc_sigreq_new_batch": (c_int, [c_p, c_sz, c_sz, c_sz, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "cc_sigreq_new_batch_device": (c_int, [c_p, c_sz, c_sz, c_sz, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "cc_sigreq_pok_init_batch": (c_int, [c_p, c_sz, c_sz, c_sz, c_p, c_p, c_p, c_p]),
+    "cc_sigreq_pok_init_batch_device": (c_int, [c_p, c_sz, c_sz, c_sz, c_p, c_p, c_p, c_p, c_p]),
+    "cc_sigreq_pok_gen_proof_batch": (c_int, [c_p, c_sz, c_sz, c_sz, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "cc_sigreq_pok_gen_proof_batch_device": (c_int, [c_p, c_sz, c_sz, c_sz, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
     "cc_vss_verify_batch": (c_int, [c_p, c_sz, c_sz, c_p, c_p, c_p, c_sz, c_p, c_p, c_p, c_p]),
     "cc_fixed_base_mul": (c_int, [c_p, c_int, c_p, c_sz, c_p, c_p]),
     "cc_rlc_partial_words": (c_int, []),

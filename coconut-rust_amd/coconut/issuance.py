@@ -1,15 +1,20 @@
-"""Issuer-side batch entry points and the holder's BlindSignature::unblind — host mirror of reference src/signature.rs:124-444 (SURVEY.md
-§8(f) row 3): BlindSignature::new (382-433) and SignatureRequestProof::verify (324-377) for whole
-batches of signature requests, and BlindSignature::unblind (436-443), through include/coconut_hip.h."""
+"""Issuance batch entry points — host mirror of reference src/signature.rs:124-444 (SURVEY.md
+§8(f) row 3).  Issuer side: BlindSignature::new (382-433) and SignatureRequestProof::verify (324-377)
+for whole batches of signature requests.  Holder side: SignatureRequest::new (124-192),
+SignatureRequestPoK::init / to_bytes / gen_proof (216-320) and BlindSignature::unblind (436-443).  All
+through include/coconut_hip.h."""
 from __future__ import annotations
 
 import ctypes
-from typing import List, Sequence
+import secrets
+from dataclasses import dataclass
+from typing import List, Optional, Sequence, Union
 
 import numpy as np
 
 from ._lib import buf, check, lib, need
-from .signature import Context
+from .errors import CoconutError
+from .signature import R_ORDER, Context, Params, fr_bytes, hash_msg
 
 
 def blind_sign_batch(ctx: Context, q: int, k: int, commitments: Sequence[bytes], known: Sequence[Sequence[bytes]],
@@ -97,3 +102,178 @@ def unblind_batch(ctx: Context, c1s: Sequence[bytes], c2s: Sequence[bytes], sks:
           "cc_unblind_batch")
     raw = out.tobytes()
     return [raw[i * sb:(i + 1) * sb] for i in range(n)]
+
+
+# ---------------------------------------------------------------- holder side: the signature request
+def _fresh_scalars(count: int) -> bytes:
+    """count scalars from the OS generator: 48 random bytes each, reduced mod r (bias < 2^-128)."""
+    return b"".join((int.from_bytes(secrets.token_bytes(48), "big") % R_ORDER).to_bytes(48, "big")
+                    for _ in range(count))
+
+
+def sigreq_proof_bytes(ctx: Context, k: int) -> int:
+    """Bytes of one request's proof record, 2 sb + 48 (k + 2) + k (2 sb + 144) (cc_sigreq_proof_bytes)."""
+    sb = ctx.mode.sig_bytes
+    return 2 * sb + 48 * (k + 2) + k * (2 * sb + 144)
+
+
+def sigreq_new_batch(ctx: Context, n: int, q: int, k: int, msgs: bytes, elgamal_pk: bytes,
+                     rand: Optional[bytes] = None):
+    """SignatureRequest::new for n requests with the first k of q messages hidden, under the context's
+    request params (Context.set_request_params; cc_sigreq_new_batch).  msgs n x q x 48, elgamal_pk n
+    encodings, rand n x (k + 1) x 48 = r | k_0 .. per request (None draws it from `secrets`).
+    Returns (commitments, hs, ciphertexts, rand): n encodings, n encodings, n x k x (c1 | c2), and the
+    randomness gen_proof needs."""
+    sb = ctx.mode.sig_bytes
+    if rand is None:
+        rand = _fresh_scalars(n * (k + 1))
+    for v, nb, what in ((msgs, n * q * 48, "messages"), (elgamal_pk, n * sb if k else 0, "ElGamal keys"),
+                        (rand, n * (k + 1) * 48, "randomness")):
+        need(v, nb, what)
+    outs = [np.zeros(max(n * w, 1), dtype=np.uint8) for w in (sb, sb, k * 2 * sb)]
+    keep = [buf(x) for x in (msgs, elgamal_pk, rand)]
+    check(lib.cc_sigreq_new_batch(ctx.h, n, q, k, keep[0][0], keep[1][0], keep[2][0],
+                                  *[ctypes.c_void_p(o.ctypes.data) for o in outs]), "cc_sigreq_new_batch")
+    cm, h, ct = (o.tobytes()[:n * w] for o, w in zip(outs, (sb, sb, k * 2 * sb)))
+    return cm, h, ct, bytes(rand)
+
+
+def sigreq_pok_init_batch(ctx: Context, n: int, q: int, k: int, h: bytes, elgamal_pk: bytes,
+                          blind: Optional[bytes] = None):
+    """SignatureRequestPoK::init for n requests (cc_sigreq_pok_init_batch): h = the hs of sigreq_new_batch,
+    blind n x (3k + 2) x 48 = b_sk | hb_0 .. hb_{k-1} | b_r | k x (b1_i | b2_i) (None draws it).
+    Returns (proofs, blind): n proof records with the T fields filled and the responses zero."""
+    sb = ctx.mode.sig_bytes
+    if blind is None:
+        blind = _fresh_scalars(n * (3 * k + 2))
+    for v, nb, what in ((h, n * sb if k else 0, "h"), (elgamal_pk, n * sb if k else 0, "ElGamal keys"),
+                        (blind, n * (3 * k + 2) * 48, "blindings")):
+        need(v, nb, what)
+    pb = sigreq_proof_bytes(ctx, k)
+    out = np.zeros(max(n * pb, 1), dtype=np.uint8)
+    keep = [buf(x) for x in (h, elgamal_pk, blind)]
+    check(lib.cc_sigreq_pok_init_batch(ctx.h, n, q, k, keep[0][0], keep[1][0], keep[2][0],
+                                       ctypes.c_void_p(out.ctypes.data)), "cc_sigreq_pok_init_batch")
+    return out.tobytes()[:n * pb], bytes(blind)
+
+
+def sigreq_pok_gen_proof_batch(ctx: Context, n: int, q: int, k: int, msgs: bytes, rand: bytes, blind: bytes,
+                               elgamal_sk: bytes, chal: bytes, proofs: bytes) -> bytes:
+    """SignatureRequestPoK::gen_proof for n committed proofs (cc_sigreq_pok_gen_proof_batch): fills the
+    response fields of `proofs` (b - chal * secret mod r) and returns the records, which
+    sigreq_verify_batch accepts as they are."""
+    pb = sigreq_proof_bytes(ctx, k)
+    for v, nb, what in ((msgs, n * q * 48, "messages"), (rand, n * (k + 1) * 48, "randomness"),
+                        (blind, n * (3 * k + 2) * 48, "blindings"), (elgamal_sk, n * 48, "ElGamal secret keys"),
+                        (chal, n * 48, "challenges"), (proofs, n * pb, "proofs")):
+        need(v, nb, what)
+    out = np.frombuffer(bytes(proofs[:n * pb]) or bytes(1), dtype=np.uint8).copy()
+    keep = [buf(x) for x in (msgs, rand, blind, elgamal_sk, chal)]
+    check(lib.cc_sigreq_pok_gen_proof_batch(ctx.h, n, q, k, keep[0][0], keep[1][0], keep[2][0], keep[3][0],
+                                            keep[4][0], ctypes.c_void_p(out.ctypes.data)),
+          "cc_sigreq_pok_gen_proof_batch")
+    return out.tobytes()[:n * pb]
+
+
+def sigreq_pok_to_bytes_batch(ctx: Context, n: int, k: int, g: bytes, h_params: Sequence[bytes], hs: bytes,
+                              elgamal_pk: bytes, proofs: bytes) -> List[bytes]:
+    """SignatureRequestPoK::to_bytes per request: every committed part is its bases in commit order, then
+    its T: g | T_sk | h_0 .. h_{k-1} | g | T_comm | k x (g | T_1i | pk | h | T_2i)."""
+    sb = ctx.mode.sig_bytes
+    pb = sigreq_proof_bytes(ctx, k)
+    hp = b"".join(bytes(x) for x in h_params[:k])
+    for v, nb, what in ((g, sb, "g"), (hp, k * sb, "h"), (hs, n * sb, "h"), (elgamal_pk, n * sb, "ElGamal keys"),
+                        (proofs, n * pb, "proofs")):
+        need(v, nb, what)
+    g = bytes(g)
+    rows = []
+    for i in range(n):
+        p = proofs[i * pb:(i + 1) * pb]
+        pk, h = elgamal_pk[i * sb:(i + 1) * sb], hs[i * sb:(i + 1) * sb]
+        row = [g, p[:sb], hp, g, p[sb + 48:2 * sb + 48]]
+        for j in range(k):
+            o = 2 * sb + 48 * (k + 2) + j * (2 * sb + 144)
+            row += [g, p[o:o + sb], pk, h, p[o + sb + 48:o + 2 * sb + 48]]
+        rows.append(b"".join(bytes(x) for x in row))
+    return rows
+
+
+def sigreq_challenge_batch(ctx: Context, n: int, k: int, g: bytes, h_params: Sequence[bytes], hs: bytes,
+                           elgamal_pk: bytes, proofs: bytes) -> bytes:
+    """The reference's challenge (signature.rs:617: FieldElement::from_msg_hash(&pok.to_bytes())) for n
+    committed proofs: the to_bytes rows through hash_msg on the GPU; n x 48 B."""
+    return b"".join(hash_msg(ctx, sigreq_pok_to_bytes_batch(ctx, n, k, g, h_params, hs, elgamal_pk, proofs)))
+
+
+@dataclass
+class SignatureRequest:
+    """signature.rs:107-112: what the holder sends the signers."""
+    known_messages: List[bytes]
+    commitment: bytes
+    ciphertexts: List[tuple]  # (c1, c2) per hidden message
+    h: bytes                  # compute_h(commitment, known), what the signers recompute
+
+    @staticmethod
+    def new(msgs: Sequence[Union[int, bytes]], count_hidden: int, elgamal_pk: bytes, params: Params,
+            ctx: Context = None, rand: Optional[Sequence[Union[int, bytes]]] = None):
+        """Returns (request, randomness) as the reference does; randomness = [r, k_0 ..] as 48-byte
+        scalars.  rand fixes the draws (replaying a recorded request)."""
+        ctx = ctx or Context.default()
+        q, k = len(msgs), int(count_hidden)
+        if q != len(params.h) or k > q:
+            raise CoconutError(-1, f"{q} messages, {k} hidden, params for {len(params.h)}")
+        if rand is not None and len(rand) != k + 1:
+            raise CoconutError(-2, f"rand holds {len(rand)} scalars, new draws {k + 1}")
+        ctx.set_request_params(params.g, params.h)
+        mb = b"".join(fr_bytes(m) for m in msgs)
+        rb = None if rand is None else b"".join(fr_bytes(x) for x in rand)
+        cm, h, ct, rb = sigreq_new_batch(ctx, 1, q, k, mb, elgamal_pk, rb)
+        sb = ctx.mode.sig_bytes
+        cts = [(ct[2 * i * sb:(2 * i + 1) * sb], ct[(2 * i + 1) * sb:(2 * i + 2) * sb]) for i in range(k)]
+        req = SignatureRequest([mb[i * 48:(i + 1) * 48] for i in range(k, q)], cm, cts, h)
+        return req, [rb[i * 48:(i + 1) * 48] for i in range(k + 1)]
+
+
+@dataclass
+class SignatureRequestPoK:
+    """signature.rs:205-213: the committed state between init and gen_proof."""
+    proof: bytes             # the proof record: T fields set, responses zero until gen_proof
+    k: int
+    q: int
+    g: bytes
+    h_params: List[bytes]
+    h: bytes
+    elgamal_pk: bytes
+    blind: bytes             # b_sk | hb_0 .. | b_r | k x (b1_i | b2_i) (secret)
+    ctx: Context = None
+
+    @staticmethod
+    def init(sig_req: SignatureRequest, elgamal_pk: bytes, params: Params, ctx: Context = None,
+             blind: Optional[Sequence[Union[int, bytes]]] = None) -> "SignatureRequestPoK":
+        ctx = ctx or Context.default()
+        k = len(sig_req.ciphertexts)
+        q = k + len(sig_req.known_messages)
+        if blind is not None and len(blind) != 3 * k + 2:
+            raise CoconutError(-2, f"blind holds {len(blind)} scalars, init draws {3 * k + 2}")
+        ctx.set_request_params(params.g, params.h)
+        bb = None if blind is None else b"".join(fr_bytes(x) for x in blind)
+        proof, bb = sigreq_pok_init_batch(ctx, 1, q, k, sig_req.h, elgamal_pk, bb)
+        return SignatureRequestPoK(proof, k, q, bytes(params.g), [bytes(x) for x in params.h], sig_req.h,
+                                   bytes(elgamal_pk), bb, ctx)
+
+    def to_bytes(self) -> bytes:
+        ctx = self.ctx or Context.default()
+        return sigreq_pok_to_bytes_batch(ctx, 1, self.k, self.g, self.h_params, self.h, self.elgamal_pk, self.proof)[0]
+
+    def gen_proof(self, hidden_msgs: Sequence[Union[int, bytes]], randomness: Sequence[Union[int, bytes]],
+                  elgamal_sk: Union[int, bytes], chal: Union[int, bytes]) -> bytes:
+        """hidden_msgs: the k hidden messages; randomness: what SignatureRequest.new returned.  Returns the
+        proof record sigreq_verify_batch reads."""
+        ctx = self.ctx or Context.default()
+        if len(hidden_msgs) != self.k or len(randomness) != self.k + 1:
+            raise CoconutError(-2, f"{len(hidden_msgs)} hidden messages and {len(randomness)} scalars for k = {self.k}")
+        # gen_proof reads the first k of q messages; the known ones are not part of any response
+        mb = b"".join(fr_bytes(m) for m in hidden_msgs) + bytes(48 * (self.q - self.k))
+        rb = b"".join(fr_bytes(x) for x in randomness)
+        return sigreq_pok_gen_proof_batch(ctx, 1, self.q, self.k, mb, rb, self.blind, fr_bytes(elgamal_sk),
+                                          fr_bytes(chal), self.proof)

@@ -142,6 +142,7 @@ class Context:
         self._vk = None
         self._timing = False
         self._iss_q = 0
+        self._rq = None
 
     @classmethod
     def default(cls, device: int = 0, mode: GroupMode = GroupMode.SIG_G2) -> "Context":
@@ -198,6 +199,26 @@ class Context:
         py, k2 = buf(Y)
         check(lib.cc_set_issuers(self.h, len(ids), q, ctypes.c_void_p(ids.ctypes.data), px, py), "cc_set_issuers")
         self._iss_q = q
+
+    def set_request_params(self, g: bytes, h: Sequence[bytes], table_bits: int = 0):
+        """Params.g and Params.h for the holder side of issuance (cc_set_request_params): builds the
+        SignatureGroup fixed-base tables sigreq_new_batch / sigreq_pok_init_batch read.  table_bits in
+        8..16 forces the window width, 0 picks one by memory (and keeps tables already built for the
+        same g and h, whatever their width)."""
+        hb = b"".join(h) if not isinstance(h, (bytes, bytearray)) else bytes(h)
+        sb = self.mode.sig_bytes
+        q = len(hb) // sb
+        need(g, sb, "g")
+        need(hb, max(q, 1) * sb, "h")
+        key = (bytes(g), hb, int(table_bits))
+        # the same params again: the tables stand (table_bits = 0 asks for no particular width)
+        if self._rq is not None and self._rq[:2] == key[:2] and table_bits in (0, self._rq[2]):
+            return
+        pg, k1 = buf(g)
+        ph, k2 = buf(hb)
+        self._rq = None  # a failed call leaves the context without request params
+        check(lib.cc_set_request_params(self.h, q, pg, ph, int(table_bits)), "cc_set_request_params")
+        self._rq = key
 
     def set_concurrency(self, slots: int):
         """cc_set_concurrency: K verify batches in flight on K caller streams (workspace slots taken

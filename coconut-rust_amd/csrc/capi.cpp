@@ -115,6 +115,19 @@ int cck_pok_responses(size_t n, int q, int r, const uint8_t* d_msgs, const uint8
                       const uint32_t* d_rev_idx, uint8_t* d_out, hipStream_t st);
 int cck_unblind_assemble(int group, size_t n, const uint8_t* d_c1, const uint8_t* d_c2, const uint8_t* d_sk,
                          uint8_t* d_pts, uint32_t* d_sc, hipStream_t st);
+size_t cck_rq_table_words(int group, size_t n);
+size_t cck_rq_digit_bytes(size_t n, int k);
+int cck_rq_fixed(int group, size_t n, int q, int k, int init, const uint8_t* d_msgs, const uint8_t* d_rnd,
+                 const uint32_t* d_table, int wbits, const uint32_t* d_binf, uint8_t* d_long, uint8_t* d_out,
+                 hipStream_t st);
+int cck_rq_two_base(int group, size_t n, int q, int k, int init, const uint8_t* d_pk, const uint8_t* d_h,
+                    const uint8_t* d_msgs, const uint8_t* d_rnd, uint32_t* d_tab, int8_t* d_digs, uint8_t* d_out,
+                    hipStream_t st);
+int cck_rq_h_rows(int group, size_t n, int q, int k, const uint8_t* d_commitment, const uint8_t* d_msgs,
+                  uint8_t* d_data, uint64_t* d_offsets, hipStream_t st);
+int cck_rq_responses(int group, size_t n, int q, int k, const uint8_t* d_msgs, const uint8_t* d_rnd,
+                     const uint8_t* d_blind, const uint8_t* d_sk, const uint8_t* d_chal, uint8_t* d_proofs,
+                     hipStream_t st);
 }
 
 namespace {
@@ -268,6 +281,15 @@ struct cc_ctx {
     DevBuf rlc_pts, rlc_dig, rlc_work, rlc_pw, rlc_finf;
     DevBuf pok_idx;  // revealed indices of the last PoK batch
     DevBuf prove_idx, prove_scratch;  // holder side (pok_prove.hip): revealed indices, sigma' entry tables
+    // request params (cc_set_request_params): SignatureGroup fixed-base tables of [h_0 .. h_{q-1}, g] for
+    // SignatureRequest::new / SignatureRequestPoK::init (sigreq_prove.hip), apart from the verkey's
+    bool have_rq = false;
+    size_t rq_q = 0;
+    int rq_wbits = 8;
+    DevBuf rq_aff, rq_inf, rq_table;
+    // their workspaces: per-request (pk, h) window tables, the two-base tasks' digits, compute_h's input
+    // rows, offsets and failure flag
+    DevBuf rq_tab, rq_dig, rq_hdata, rq_hoff, rq_fail;
     int n_simd = 0;  // SIMDs of the device (4 a CU), read once (pok_rlc_twin)
     // issuer table (cc_set_issuers): sorted ids, decoded verkeys, per-base 8-bit window tables
     size_t iss_n = 0, iss_q = 0;
@@ -471,7 +493,8 @@ cc_status cc_ctx_destroy(cc_ctx* c) {
                       &c->rlc_key, &c->rlc_any, &c->rlc_part, &c->rlc_flag, &c->rlc_accept, &c->fin_f, &c->fin_scratch, &c->fin_prep, &c->fin_flags2, &c->fin_part, &c->pok_idx, &c->rlc_gath,
                       &c->rlc_pts, &c->rlc_dig, &c->rlc_work, &c->rlc_pw, &c->rlc_finf,
                       &c->iss_ids, &c->iss_aff, &c->iss_inf, &c->iss_table, &c->agg_scratch, &c->dev_err,
-                      &c->prove_idx, &c->prove_scratch};
+                      &c->prove_idx, &c->prove_scratch, &c->rq_aff, &c->rq_inf, &c->rq_table, &c->rq_tab, &c->rq_dig,
+                      &c->rq_hdata, &c->rq_hoff, &c->rq_fail};
     for (auto* b : bufs) b->release();
     for (auto& b : c->in_aux) b.release();
     for (auto& e : c->ev) if (e) (void)hipEventDestroy(e);
@@ -2197,6 +2220,290 @@ cc_status cc_unblind_batch(cc_ctx* c, size_t n, const uint8_t* c1, const uint8_t
     const bool wiped = hipMemsetAsync(dK.p, 0, n * 48, st) == hipSuccess &&
                        hipMemsetAsync(dS.p, 0, n * 64, st) == hipSuccess &&
                        hipMemsetAsync(c->agg_scratch.p, 0, scr, st) == hipSuccess;
+    if (hipStreamSynchronize(st) != hipSuccess || !wiped) return s ? s : CC_ERR_HIP;
+    return s;
+}
+
+// ---------------------------------------------------------------- holder side of issuance (sigreq_prove.hip)
+// default HBM budget of the request params' tables (at most half of what is free).  The widest
+// candidate, 16 bits, takes 0.10 / 0.20 GB a G1 / G2 base, so 4 GiB holds it up to q = 39 / 19.
+constexpr double kRqTableBudget = 4.0 * (double)(1ull << 30);
+
+cc_status cc_set_request_params(cc_ctx* c, size_t q, const uint8_t* g, const uint8_t* h, int table_bits) {
+    c = primary(c);  // a device set forwards to its first device
+    if (!c || !g || !h || q == 0 || q > kMaxQ || (table_bits != 0 && (table_bits < 8 || table_bits > 16)))
+        return CC_ERR_DECODE;
+    // no request params until every step below has succeeded (as cc_set_issuers)
+    c->have_rq = false;
+    c->rq_q = 0;
+    HIPCK(hipSetDevice(c->device));
+    drain_slots(c);  // concurrent device batches before the tables are rebuilt
+    HIPCK(hipStreamSynchronize(c->stream));  // an asynchronous *_device call may still read the old tables
+    const int sg = sig_group(c->mode);
+    const size_t sb = (size_t)sig_bytes(c->mode), aw = aff_words(sg), nb = q + 1;
+    std::vector<uint8_t> enc(nb * sb);  // [h_0 .. h_{q-1}, g]: g is table base q
+    memcpy(enc.data(), h, q * sb);
+    memcpy(enc.data() + q * sb, g, sb);
+    // the old table is released first so its memory counts as free (identical calls pick the same width)
+    c->rq_table.release();
+    const double budget = std::min(kRqTableBudget, 0.5 * (double)free_hbm());
+    int wb = 8;
+    if (table_bits) {
+        wb = table_bits;
+    } else {
+        for (int cand : {16, 13, 12, 10})
+            if ((double)(nb * tab_words(sg, cand) * 4) <= budget) {
+                wb = cand;
+                break;
+            }
+    }
+    if (c->rq_aff.ensure(nb * aw * 4) || c->rq_inf.ensure(nb * 4)) return CC_ERR_HIP;
+    const double fr = (double)free_hbm();
+    if (fr > 0 && (double)(nb * tab_words(sg, wb) * 4) > 0.9 * fr) {  // see rebuild_tables
+        if (table_bits || wb == 8) return CC_ERR_HIP;
+        wb = 8;
+    }
+    if (c->rq_table.ensure(nb * tab_words(sg, wb) * 4)) {
+        (void)hipGetLastError();  // clear the failed allocation's error
+        if (table_bits || wb == 8) return CC_ERR_HIP;
+        wb = 8;                   // the wide table did not fit the free HBM
+        if (c->rq_table.ensure(nb * tab_words(sg, wb) * 4)) return CC_ERR_HIP;
+    }
+    cc_status s = decode_points_host(c, sg, nb, enc.data(), c->rq_aff.as<uint32_t>(), c->rq_inf.as<uint32_t>());
+    if (s) return s;
+    DevBuf pw;
+    if (pw.ensure(nb * tab_nwin(wb) * (sg == 1 ? 36 : 72) * 4)) return CC_ERR_HIP;
+    // lazy form: the sums read the tables through ft_add_lz / pl::ft_add_g2_lz
+    KCK(cck_build_table(sg, (int)nb, wb, c->rq_aff.as<uint32_t>(), c->rq_inf.as<uint32_t>(), pw.as<uint32_t>(),
+                        c->rq_table.as<uint32_t>(), 1, c->stream));
+    HIPCK(hipStreamSynchronize(c->stream));
+    pw.release();
+    c->rq_q = q;
+    c->rq_wbits = wb;
+    c->have_rq = true;
+    return CC_OK;
+}
+
+// the checks after the NULL checks, in the header's order; with_params: new and init read the tables
+static cc_status rq_checks(const cc_ctx* c, bool with_params, size_t n, size_t q, size_t k) {
+    if (with_params) {
+        if (!c->have_rq) return CC_ERR_STATE;
+        if (q != c->rq_q) return CC_ERR_LEN;
+    } else if (q > kMaxQ) {
+        return CC_ERR_DECODE;
+    }
+    if (k > q) return CC_ERR_LEN;
+    if (n > kMaxBatch) return CC_ERR_DECODE;
+    return CC_OK;
+}
+
+static cc_status rq_ensure_two(cc_ctx* c, size_t n, size_t k) {
+    if (!k) return CC_OK;
+    if (c->rq_tab.ensure(cck_rq_table_words(sig_group(c->mode), n) * 4) ||
+        c->rq_dig.ensure(cck_rq_digit_bytes(n, (int)k)))
+        return CC_ERR_HIP;
+    return CC_OK;
+}
+
+static cc_status launch_sigreq_new(cc_ctx* c, size_t n, size_t q, size_t k, const uint8_t* d_msgs, const uint8_t* d_pk,
+                                   const uint8_t* d_rand, uint8_t* d_comm, uint8_t* d_h, uint8_t* d_cts,
+                                   hipStream_t st) {
+    const int sg = sig_group(c->mode);
+    const size_t len = (size_t)sig_bytes(c->mode) + 48 * (q - k);
+    if (c->rq_hdata.ensure(n * len + 16) || c->rq_hoff.ensure((n + 1) * 8) || c->rq_fail.ensure(4)) return CC_ERR_HIP;
+    cc_status s = rq_ensure_two(c, n, k);
+    if (s) return s;
+    KCK(cck_rq_fixed(sg, n, (int)q, (int)k, 0, d_msgs, d_rand, c->rq_table.as<uint32_t>(), c->rq_wbits,
+                     c->rq_inf.as<uint32_t>(), d_comm, d_cts, st));
+    // h = compute_h(commitment, known) as cc_blind_sign_batch computes it (compute_h_batch), rows built on
+    // the device
+    KCK(cck_rq_h_rows(sg, n, (int)q, (int)k, d_comm, d_msgs, c->rq_hdata.as<uint8_t>(), c->rq_hoff.as<uint64_t>(), st));
+    HIPCK(hipMemsetAsync(c->rq_fail.p, 0, 4, st));
+    KCK(cck_h_input_canon(sg, n, len, (int)(q - k), c->rq_hdata.as<uint8_t>(), st));
+    KCK(cck_hash_to_curve(sg, n, c->rq_hdata.as<uint8_t>(), c->rq_hoff.as<uint64_t>(), d_h, c->rq_fail.as<uint32_t>(),
+                          st));
+    KCK(cck_rq_two_base(sg, n, (int)q, (int)k, 0, d_pk, d_h, d_msgs, d_rand, c->rq_tab.as<uint32_t>(),
+                        c->rq_dig.as<int8_t>(), d_cts, st));
+    return CC_OK;
+}
+
+cc_status cc_sigreq_new_batch_device(cc_ctx* c, size_t n, size_t q, size_t k, const uint8_t* d_msgs,
+                                     const uint8_t* d_pk, const uint8_t* d_rand, uint8_t* d_comm, uint8_t* d_h,
+                                     uint8_t* d_cts, void* stream) {
+    c = primary(c);  // a device set forwards to its first device
+    if (!c || (n && (!d_rand || !d_comm || !d_h || (q && !d_msgs) || (k && (!d_pk || !d_cts))))) return CC_ERR_DECODE;
+    cc_status s = rq_checks(c, true, n, q, k);
+    if (s) return s;
+    if (!n) return CC_OK;
+    HIPCK(hipSetDevice(c->device));
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    StreamOrder order(c, st);
+    return launch_sigreq_new(c, n, q, k, d_msgs, d_pk, d_rand, d_comm, d_h, d_cts, st);
+}
+
+cc_status cc_sigreq_new_batch(cc_ctx* c, size_t n, size_t q, size_t k, const uint8_t* msgs, const uint8_t* pk,
+                              const uint8_t* rand, uint8_t* out_comm, uint8_t* out_h, uint8_t* out_cts) {
+    c = primary(c);  // a device set forwards to its first device
+    if (!c || (n && (!rand || !out_comm || !out_h || (q && !msgs) || (k && (!pk || !out_cts))))) return CC_ERR_DECODE;
+    cc_status s = rq_checks(c, true, n, q, k);
+    if (s) return s;
+    if (!n) return CC_OK;
+    HIPCK(hipSetDevice(c->device));
+    drain_slots(c);  // concurrent device batches (cc_set_concurrency) before the workspaces are resized
+    const size_t sb = (size_t)sig_bytes(c->mode), rb = n * (k + 1) * 48, mb = n * q * 48;
+    hipStream_t st = c->stream;
+    DevBuf& dR = c->in_aux[0];
+    DevBuf& dP = c->in_aux[1];
+    DevBuf& dC = c->in_aux[2];
+    DevBuf& dH = c->in_aux[3];
+    DevBuf& dT = c->in_aux[4];
+    if (c->in_msgs.ensure(mb + 16) || dR.ensure(rb) || dP.ensure(n * sb) || dC.ensure(n * sb) || dH.ensure(n * sb) ||
+        dT.ensure(n * k * 2 * sb + 16))
+        return CC_ERR_HIP;
+    s = rq_ensure_two(c, n, k);  // before run(): the wipe below covers the digits of this call
+    if (s) return s;
+    uint32_t fail = 0;
+    auto run = [&]() -> cc_status {
+        HIPCK(hipMemcpyAsync(c->in_msgs.p, msgs, mb, hipMemcpyHostToDevice, st));
+        HIPCK(hipMemcpyAsync(dR.p, rand, rb, hipMemcpyHostToDevice, st));
+        if (k) HIPCK(hipMemcpyAsync(dP.p, pk, n * sb, hipMemcpyHostToDevice, st));
+        cc_status e = launch_sigreq_new(c, n, q, k, c->in_msgs.as<uint8_t>(), dP.as<uint8_t>(), dR.as<uint8_t>(),
+                                        dC.as<uint8_t>(), dH.as<uint8_t>(), dT.as<uint8_t>(), st);
+        if (e) return e;
+        HIPCK(hipMemcpyAsync(out_comm, dC.p, n * sb, hipMemcpyDeviceToHost, st));
+        HIPCK(hipMemcpyAsync(out_h, dH.p, n * sb, hipMemcpyDeviceToHost, st));
+        if (k) HIPCK(hipMemcpyAsync(out_cts, dT.p, n * k * 2 * sb, hipMemcpyDeviceToHost, st));
+        HIPCK(hipMemcpyAsync(&fail, c->rq_fail.p, 4, hipMemcpyDeviceToHost, st));
+        return CC_OK;
+    };
+    s = run();
+    // the device copies of the secrets (the messages, r and the k_i, the digits of k_i and m_i) are zeroed
+    bool wiped = hipMemsetAsync(c->in_msgs.p, 0, mb, st) == hipSuccess && hipMemsetAsync(dR.p, 0, rb, st) == hipSuccess;
+    if (k) wiped = hipMemsetAsync(c->rq_dig.p, 0, cck_rq_digit_bytes(n, (int)k), st) == hipSuccess && wiped;
+    if (hipStreamSynchronize(st) != hipSuccess || !wiped) return s ? s : CC_ERR_HIP;
+    if (!s && fail) return CC_ERR_DECODE;  // as cc_hash_to_curve: 4,096 failed tries
+    return s;
+}
+
+static cc_status launch_sigreq_init(cc_ctx* c, size_t n, size_t q, size_t k, const uint8_t* d_h, const uint8_t* d_pk,
+                                    const uint8_t* d_blind, uint8_t* d_proofs, hipStream_t st) {
+    const int sg = sig_group(c->mode);
+    cc_status s = rq_ensure_two(c, n, k);
+    if (s) return s;
+    HIPCK(hipMemsetAsync(d_proofs, 0, n * cck_sigreq_proof_bytes(sg, (int)k), st));  // the response fields
+    KCK(cck_rq_fixed(sg, n, (int)q, (int)k, 1, nullptr, d_blind, c->rq_table.as<uint32_t>(), c->rq_wbits,
+                     c->rq_inf.as<uint32_t>(), d_proofs, d_proofs, st));
+    KCK(cck_rq_two_base(sg, n, (int)q, (int)k, 1, d_pk, d_h, nullptr, d_blind, c->rq_tab.as<uint32_t>(),
+                        c->rq_dig.as<int8_t>(), d_proofs, st));
+    return CC_OK;
+}
+
+cc_status cc_sigreq_pok_init_batch_device(cc_ctx* c, size_t n, size_t q, size_t k, const uint8_t* d_h,
+                                          const uint8_t* d_pk, const uint8_t* d_blind, uint8_t* d_proofs,
+                                          void* stream) {
+    c = primary(c);  // a device set forwards to its first device
+    if (!c || (n && (!d_blind || !d_proofs || (k && (!d_h || !d_pk))))) return CC_ERR_DECODE;
+    cc_status s = rq_checks(c, true, n, q, k);
+    if (s) return s;
+    if (!n) return CC_OK;
+    HIPCK(hipSetDevice(c->device));
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    StreamOrder order(c, st);
+    return launch_sigreq_init(c, n, q, k, d_h, d_pk, d_blind, d_proofs, st);
+}
+
+cc_status cc_sigreq_pok_init_batch(cc_ctx* c, size_t n, size_t q, size_t k, const uint8_t* h, const uint8_t* pk,
+                                   const uint8_t* blind, uint8_t* out_proofs) {
+    c = primary(c);  // a device set forwards to its first device
+    if (!c || (n && (!blind || !out_proofs || (k && (!h || !pk))))) return CC_ERR_DECODE;
+    cc_status s = rq_checks(c, true, n, q, k);
+    if (s) return s;
+    if (!n) return CC_OK;
+    HIPCK(hipSetDevice(c->device));
+    drain_slots(c);  // concurrent device batches (cc_set_concurrency) before the workspaces are resized
+    const size_t sb = (size_t)sig_bytes(c->mode), bb = n * (3 * k + 2) * 48;
+    const size_t pb = n * cck_sigreq_proof_bytes(sig_group(c->mode), (int)k);
+    hipStream_t st = c->stream;
+    DevBuf& dB = c->in_aux[0];
+    DevBuf& dP = c->in_aux[1];
+    DevBuf& dH = c->in_aux[2];
+    DevBuf& dO = c->in_aux[3];
+    if (dB.ensure(bb) || dP.ensure(n * sb) || dH.ensure(n * sb) || dO.ensure(pb)) return CC_ERR_HIP;
+    s = rq_ensure_two(c, n, k);
+    if (s) return s;
+    auto run = [&]() -> cc_status {
+        HIPCK(hipMemcpyAsync(dB.p, blind, bb, hipMemcpyHostToDevice, st));
+        if (k) {
+            HIPCK(hipMemcpyAsync(dP.p, pk, n * sb, hipMemcpyHostToDevice, st));
+            HIPCK(hipMemcpyAsync(dH.p, h, n * sb, hipMemcpyHostToDevice, st));
+        }
+        cc_status e = launch_sigreq_init(c, n, q, k, dH.as<uint8_t>(), dP.as<uint8_t>(), dB.as<uint8_t>(),
+                                         dO.as<uint8_t>(), st);
+        if (e) return e;
+        HIPCK(hipMemcpyAsync(out_proofs, dO.p, pb, hipMemcpyDeviceToHost, st));
+        return CC_OK;
+    };
+    s = run();
+    // the device copies of the blindings and of the digits of b2_i and hb_i are zeroed
+    bool wiped = hipMemsetAsync(dB.p, 0, bb, st) == hipSuccess;
+    if (k) wiped = hipMemsetAsync(c->rq_dig.p, 0, cck_rq_digit_bytes(n, (int)k), st) == hipSuccess && wiped;
+    if (hipStreamSynchronize(st) != hipSuccess || !wiped) return s ? s : CC_ERR_HIP;
+    return s;
+}
+
+cc_status cc_sigreq_pok_gen_proof_batch_device(cc_ctx* c, size_t n, size_t q, size_t k, const uint8_t* d_msgs,
+                                               const uint8_t* d_rand, const uint8_t* d_blind, const uint8_t* d_sk,
+                                               const uint8_t* d_chal, uint8_t* d_proofs, void* stream) {
+    c = primary(c);  // a device set forwards to its first device
+    if (!c || (n && (!d_rand || !d_blind || !d_sk || !d_chal || !d_proofs || (k && !d_msgs)))) return CC_ERR_DECODE;
+    cc_status s = rq_checks(c, false, n, q, k);
+    if (s) return s;
+    if (!n) return CC_OK;
+    HIPCK(hipSetDevice(c->device));
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    StreamOrder order(c, st);
+    KCK(cck_rq_responses(sig_group(c->mode), n, (int)q, (int)k, d_msgs, d_rand, d_blind, d_sk, d_chal, d_proofs, st));
+    return CC_OK;
+}
+
+cc_status cc_sigreq_pok_gen_proof_batch(cc_ctx* c, size_t n, size_t q, size_t k, const uint8_t* msgs,
+                                        const uint8_t* rand, const uint8_t* blind, const uint8_t* sk,
+                                        const uint8_t* chal, uint8_t* proofs) {
+    c = primary(c);  // a device set forwards to its first device
+    if (!c || (n && (!rand || !blind || !sk || !chal || !proofs || (k && !msgs)))) return CC_ERR_DECODE;
+    cc_status s = rq_checks(c, false, n, q, k);
+    if (s) return s;
+    if (!n) return CC_OK;
+    HIPCK(hipSetDevice(c->device));
+    drain_slots(c);  // concurrent device batches (cc_set_concurrency) before the workspaces are resized
+    const size_t rb = n * (k + 1) * 48, bb = n * (3 * k + 2) * 48, mb = n * q * 48;
+    const size_t pb = n * cck_sigreq_proof_bytes(sig_group(c->mode), (int)k);
+    hipStream_t st = c->stream;
+    DevBuf& dR = c->in_aux[0];
+    DevBuf& dB = c->in_aux[1];
+    DevBuf& dK = c->in_aux[2];
+    DevBuf& dC = c->in_aux[3];
+    DevBuf& dO = c->in_aux[4];
+    if (c->in_msgs.ensure(mb + 16) || dR.ensure(rb) || dB.ensure(bb) || dK.ensure(n * 48) || dC.ensure(n * 48) ||
+        dO.ensure(pb))
+        return CC_ERR_HIP;
+    auto run = [&]() -> cc_status {
+        if (k) HIPCK(hipMemcpyAsync(c->in_msgs.p, msgs, mb, hipMemcpyHostToDevice, st));
+        HIPCK(hipMemcpyAsync(dR.p, rand, rb, hipMemcpyHostToDevice, st));
+        HIPCK(hipMemcpyAsync(dB.p, blind, bb, hipMemcpyHostToDevice, st));
+        HIPCK(hipMemcpyAsync(dK.p, sk, n * 48, hipMemcpyHostToDevice, st));
+        HIPCK(hipMemcpyAsync(dC.p, chal, n * 48, hipMemcpyHostToDevice, st));
+        HIPCK(hipMemcpyAsync(dO.p, proofs, pb, hipMemcpyHostToDevice, st));
+        KCK(cck_rq_responses(sig_group(c->mode), n, (int)q, (int)k, c->in_msgs.as<uint8_t>(), dR.as<uint8_t>(),
+                             dB.as<uint8_t>(), dK.as<uint8_t>(), dC.as<uint8_t>(), dO.as<uint8_t>(), st));
+        HIPCK(hipMemcpyAsync(proofs, dO.p, pb, hipMemcpyDeviceToHost, st));
+        return CC_OK;
+    };
+    s = run();
+    // the device copies of the messages, r and the k_i, the blindings and the ElGamal key are zeroed
+    bool wiped = hipMemsetAsync(dR.p, 0, rb, st) == hipSuccess && hipMemsetAsync(dB.p, 0, bb, st) == hipSuccess &&
+                 hipMemsetAsync(dK.p, 0, n * 48, st) == hipSuccess;
+    if (k) wiped = hipMemsetAsync(c->in_msgs.p, 0, mb, st) == hipSuccess && wiped;
     if (hipStreamSynchronize(st) != hipSuccess || !wiped) return s ? s : CC_ERR_HIP;
     return s;
 }

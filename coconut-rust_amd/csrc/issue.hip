@@ -14,6 +14,7 @@
 //     checks with the response-equality rule proof_2.responses[1] == proof_commitment.responses[i].
 #include "codec.h"
 #include "fr.h"
+#include "sigreq_layout.h"  // ProofLayout: the proof record of cc_sigreq_verify_batch
 
 using namespace cc;
 
@@ -28,17 +29,6 @@ DEV bool dec_pt<Fp2>(Aff<Fp2>& a, const uint8_t* p) { return g2_decode(a, p); }
 
 template <class F>
 constexpr int eb() { return sizeof(F) == sizeof(Fp) ? 97 : 192; }
-
-// byte offsets inside one request's proof record (layout of cc_sigreq_verify_batch)
-struct ProofLayout {
-    size_t sb, k;
-    __host__ __device__ size_t t_sk() const { return 0; }
-    __host__ __device__ size_t r_sk() const { return sb; }
-    __host__ __device__ size_t t_comm() const { return sb + 48; }
-    __host__ __device__ size_t r_comm(size_t i) const { return 2 * sb + 48 + 48 * i; }
-    __host__ __device__ size_t ct(size_t i) const { return 2 * sb + 48 * (k + 2) + i * (2 * sb + 144); }
-    __host__ __device__ size_t bytes() const { return ct(k); }
-};
 
 }  // namespace
 

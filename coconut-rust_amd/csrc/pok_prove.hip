@@ -15,18 +15,13 @@
 //   gen_proof: k_pok_responses, one lane per (proof, response): b - chal * secret mod r.
 //   unblind: k_unblind_assemble lays (c1, c2) and (-sk, 1) out for the windowed Straus MSM
 //     (aggregate.hip k_msm_straus, t = 2).
-#include "codec.h"
-#include "curve_lz.h"
-#include "curve_pl.h"
 #include "fixed.h"
-#include "fr.h"
-#include "straus.h"
+#include "prove_common.h"
 
 using namespace cc;
 
 namespace {
 
-constexpr int SP_ENT = 16;                  // entries: d sigma_1 (0..7), d sigma_2 (8..15), d = 1..8
 constexpr int SP_DIGW = (2 * 65 + 3) / 4;   // digits of r1 and of r1 r2
 constexpr int SP_PB = 128;                  // SigG2: proofs per block (one lane pair each)
 constexpr int SP_LB = 64;                   // SigG1: proofs per block (one lane each)
@@ -53,47 +48,10 @@ DEV void sp_digits(int8_t* dig, const uint8_t* rnd) {
     recode_w4(dig + 65, b);
 }
 
-// affine encoding (amcl_wrapper to_bytes) of a lane-pair point; lane h = 0 writes
-DEV void g2lz_out(const lz::JL& acc, int h, uint8_t* out) {
-    using namespace lz;
-    cc::Aff<cc::Fp2> o;
-    const bool fin = !jl_is_inf(acc);
-    pl::Fp2 x, y;
-    if (fin) {
-        const auto zi = inv(acc.z);
-        const auto zi2 = sqrr(zi);
-        x = out_r2(mulr(acc.x, zi2));
-        y = out_r2(mulr(acc.y, mulr(zi2, zi)));
-    } else {
-        fp_zero(x.c);
-        fp_zero(y.c);
-    }
-    const Fp xs = pl::swp(x.c), ys = pl::swp(y.c);
-    o.x.a = h ? xs : x.c;
-    o.x.b = h ? x.c : xs;
-    o.y.a = h ? ys : y.c;
-    o.y.b = h ? y.c : ys;
-    if (!h) g2_encode(out, o, fin);
-}
-
-DEV void g1lz_out(const lz::JG& acc, uint8_t* out) {
-    Jac<Fp> s = lz::jg_to(acc);
-    Aff<Fp> a;
-    const bool fin = jac_to_aff(a, s);
-    g1_encode(out, a, fin);
-}
-
 DEV bool pp_revealed(int hh, int r, const uint32_t* rev_idx) {
     bool rv = false;
     for (int z = 0; z < r; z++) rv |= rev_idx[z] == (uint32_t)hh;
     return rv;
-}
-
-DEV void store_fr_be48(uint8_t* p, const uint32_t v[8]) {
-    Fp c;
-#pragma unroll
-    for (int k = 0; k < NL; k++) c.v[k] = k < 8 ? v[k] : 0u;
-    store_be48_aligned(p, c);
 }
 
 }  // namespace
@@ -117,55 +75,14 @@ __global__ __launch_bounds__(256, 2) void k_sigma_prime_g2(size_t n, size_t rstr
     uint32_t* pre = zs + SP_ENT * 2 * LN;
     int8_t* dig = reinterpret_cast<int8_t*>(pre + SP_ENT * 2 * LN);
     sp_digits(dig, rnd + i * rstride * 48);  // both lanes write the same digits
+    // the multiples 1..8 of sigma_1 (entries 0..7) and sigma_2 (8..15), one inversion (prove_common.h)
     F2R acc_z = r_one();
-#pragma unroll 1
-    for (int k = 0; k < 2; k++) {
-        cc::Aff<cc::Fp2> P1;
-        const bool ok = pl::pair_all(g2_decode(P1, (k ? s2b : s1b) + i * 192));  // both lanes decode the point
-        pl::Fp2 hx, hy;
-        hx.c = h ? P1.x.b : P1.x.a;
-        hy.c = h ? P1.y.b : P1.y.a;
-        const AL P{reduce(in_r2(hx)), reduce(in_r2(hy))};
-        JL J = ok ? jl_from_aff(P) : jl_inf();
-#pragma unroll 1
-        for (int d = 0; d < 8; d++) {
-            if (d == 1) J = jl_dbl(J);
-            else if (d > 1 && ok) J = jl_add_aff(J, P);
-            const int e = k * 8 + d;
-            uint32_t* w = ent + (e * 2 + h) * SEW;
-            const bool inf = jl_is_inf(J);
-            st_w(w, J.x);
-            st_w(w + SEY, J.y);
-            w[SEF] = inf ? 1u : 0u;
-            st_w(zs + (e * 2 + h) * LN, J.z);
-            st_w(pre + (e * 2 + h) * LN, acc_z);
-            if (!inf) acc_z = reduce(mulr(acc_z, J.z));
-        }
-    }
-    // one inversion for the 16 entries, then walk back: z_e^-1 = inv * prefix_e; inv *= z_e
-    F2R zinv = reduce(inv(acc_z));
-#pragma unroll 1
-    for (int e = SP_ENT - 1; e >= 0; e--) {
-        uint32_t* w = ent + (e * 2 + h) * SEW;
-        if (w[SEF]) continue;  // identity multiple (pair-uniform: both halves carry the flag)
-        const F2R z = ld_w(zs + (e * 2 + h) * LN);
-        const auto zi = mulr(zinv, ld_w(pre + (e * 2 + h) * LN));
-        zinv = reduce(mulr(zinv, z));
-        const auto zi2 = sqrr(zi);
-        st_w(w, reduce(mulr(ld_w(w), zi2)));
-        st_w(w + SEY, reduce(mulr(ld_w(w + SEY), mulr(zi2, zi))));
-    }
+    sp_fill_g2(ent, zs, pre, h, 0, s1b + i * 192, acc_z);
+    sp_fill_g2(ent, zs, pre, h, 1, s2b + i * 192, acc_z);
+    sp_norm_g2(ent, zs, pre, h, acc_z);
     // A += d(r1) sigma_1;  B += d(r1) sigma_2 + d(r1 r2) sigma_1
     JL A = jl_inf(), B = jl_inf();
-    auto add_entry = [&](JL& acc, int base, int d) {
-        const uint32_t* w = ent + (((base * 8 + (d < 0 ? -d : d) - 1) * 2) + h) * SEW;
-        if (w[SEF]) return;  // identity multiple
-        AL e;
-        ld16(e.x.c.v, w);
-        ld16(e.y.c.v, w + SEY);
-        if (d < 0) e = jl_neg_aff(e);
-        acc = jl_add_aff(acc, e);
-    };
+    auto add_entry = [&](JL& acc, int base, int d) { sp_add_g2(acc, ent, h, base, d); };
 #pragma unroll 1
     for (int win = 64; win >= 0; win--) {
         if (win != 64) {
@@ -204,51 +121,11 @@ __global__ __launch_bounds__(SP_LB) void k_sigma_prime_g1(size_t n, size_t rstri
     int8_t* dig = reinterpret_cast<int8_t*>(pre + SP_ENT * LN);
     sp_digits(dig, rnd + i * rstride * 48);
     FR acc_z = r1_one();
-#pragma unroll 1
-    for (int k = 0; k < 2; k++) {
-        cc::Aff<cc::Fp> P1;
-        const bool ok = g1_decode(P1, (k ? s2b : s1b) + i * 97);
-        const FR px = reduce(in_r(P1.x)), py = reduce(in_r(P1.y));
-        const AG P = ag_of(px, py);
-        JG J = ok ? JG{px, py, r1_one()} : jg_inf();
-#pragma unroll 1
-        for (int d = 0; d < 8; d++) {
-            if (d == 1) J = jg_dbl(J);
-            else if (d > 1 && ok) J = jg_add_aff(J, P);
-            const int e = k * 8 + d;
-            uint32_t* w = ent + e * SEW;
-            const bool inf = jg_is_inf(J);
-            st_r1(w, J.x);
-            st_r1(w + SEY, J.y);
-            w[SEF] = inf ? 1u : 0u;
-            st_r1(zs + e * LN, J.z);
-            st_r1(pre + e * LN, acc_z);
-            if (!inf) acc_z = reduce(mulr1(acc_z, J.z));
-        }
-    }
-    cc::Fp zinv_s;
-    fp_inv(zinv_s, out_r(acc_z));
-    FR zinv = reduce(in_r(zinv_s));
-#pragma unroll 1
-    for (int e = SP_ENT - 1; e >= 0; e--) {
-        uint32_t* w = ent + e * SEW;
-        if (w[SEF]) continue;  // identity multiple
-        const FR z = ld_r1(zs + e * LN);
-        const FR zi = reduce(mulr1(zinv, ld_r1(pre + e * LN)));
-        zinv = reduce(mulr1(zinv, z));
-        const FR zi2 = reduce(sqrr1(zi));
-        st_r1(w, reduce(mulr1(ld_r1(w), zi2)));
-        st_r1(w + SEY, reduce(mulr1(ld_r1(w + SEY), mulr1(zi2, zi))));
-    }
+    sp_fill_g1(ent, zs, pre, 0, s1b + i * 97, acc_z);
+    sp_fill_g1(ent, zs, pre, 1, s2b + i * 97, acc_z);
+    sp_norm_g1(ent, zs, pre, acc_z);
     JG A = jg_inf(), B = jg_inf();
-    auto add_entry = [&](JG& acc, int base, int d) {
-        const uint32_t* w = ent + (base * 8 + (d < 0 ? -d : d) - 1) * SEW;
-        if (w[SEF]) return;  // identity multiple
-        FR ex, ey;
-        ld16(ex.v, w);
-        ld16(ey.v, w + SEY);
-        acc = jg_add_aff(acc, ag_of(ex, d < 0 ? neg(ey) : ey));
-    };
+    auto add_entry = [&](JG& acc, int base, int d) { sp_add_g1(acc, ent, base, d); };
 #pragma unroll 1
     for (int win = 64; win >= 0; win--) {
         if (win != 64) {

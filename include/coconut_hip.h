@@ -17,6 +17,9 @@
  *        replaces  ps_sig PoKOfSignature::init / gen_proof [EXT], called at src/pok_sig.rs:80-100
  *   cc_unblind_batch
  *        replaces  BlindSignature::unblind        src/signature.rs:436-443
+ *   cc_sigreq_new_batch / cc_sigreq_pok_init_batch / cc_sigreq_pok_gen_proof_batch
+ *        replaces  SignatureRequest::new, SignatureRequestPoK::init / gen_proof
+ *                                                 src/signature.rs:124-192, 216-320
  *   cc_set_params / cc_set_verkey
  *        the Params (src/signature.rs:13-17, only g_tilde is read by verify) and Verkey
  *        (src/signature.rs:46-49) a batch is checked against
@@ -369,6 +372,67 @@ cc_status cc_sigreq_verify_batch(cc_ctx* ctx, size_t n, size_t q, size_t k, cons
                                  const uint8_t* commitment, const uint8_t* known, const uint8_t* ciphertexts,
                                  const uint8_t* elgamal_pk, const uint8_t* proofs, const uint8_t* chal,
                                  uint8_t* verdicts);
+
+/* Holder side of issuance: SignatureRequest::new ("PrepareBlindSign", signature.rs:124-192) and
+ * SignatureRequestPoK::init / gen_proof (216-320), what cc_sigreq_verify_batch and cc_blind_sign_batch
+ * consume.  SG = a SignatureGroup encoding, pb = cc_sigreq_proof_bytes(ctx, k).
+ *
+ * cc_set_request_params binds Params.g (one SG) and Params.h (q x SG) and builds SignatureGroup
+ * fixed-base window tables for [h_0 .. h_{q-1}, g] (g is table base q).  table_bits in 8..16 forces the
+ * window width (a width that does not fit the free HBM: CC_ERR_HIP); 0 takes the widest of {16, 13, 12,
+ * 10, 8} whose tables fit min(4 GiB, half the free HBM), 8 bits if the allocation fails.  The tables are
+ * the context's own: the verkey and issuer tables and cc_set_table_bits are untouched.  An identity or
+ * undecodable base is skipped in every sum.  NULL ctx, g or h, q = 0, q > CC_MAX_Q or table_bits outside
+ * {0, 8..16}: CC_ERR_DECODE.  A failed call leaves the context without request params.
+ *
+ * cc_sigreq_new_batch, n requests with k hidden of q messages:
+ *   msgs n x q x 48 | elgamal_pk n x SG | rand n x (k + 1) x 48 = r | k_0 .. k_{k-1}  (the order of the
+ *   reference's returned randomness)
+ *   -> commitment = sum_{i<k} m_i h_i + r g,  h = compute_h(commitment, m_k .. m_{q-1}) (also for k = 0),
+ *      ciphertexts n x k x (c1_i = k_i g, c2_i = k_i pk + m_i h)
+ * cc_sigreq_pok_init_batch, h = out_h of new:
+ *   blind n x (3k + 2) x 48 = b_sk | hb_0 .. hb_{k-1} | b_r | k x (b1_i | b2_i)
+ *   -> the T fields of the proof record (layout at cc_sigreq_verify_batch): T_sk = b_sk g,
+ *      T_comm = sum hb_i h_i + b_r g, T_1i = b1_i g, T_2i = b2_i pk + hb_i h; the response fields zeroed.
+ * cc_sigreq_pok_gen_proof_batch writes only the response fields, each b - chal * secret mod r:
+ *   r_sk = b_sk - c sk, r_comm[i] = hb_i - c m_i, r_comm[k] = b_r - c r, r_1 = b1_i - c k_i,
+ *   r_2a = b2_i - c k_i, r_2b = hb_i - c m_i  (elgamal_sk, chal: n x 48).  After it `proofs` is what
+ *   cc_sigreq_verify_batch accepts.
+ * Checks, in this order and before the n = 0 shortcut: NULL context: CC_ERR_DECODE; a NULL buffer the
+ * call would read or write with n > 0 (with k = 0 elgamal_pk, h and the ciphertexts may be NULL):
+ * CC_ERR_DECODE; no request params: CC_ERR_STATE (new, init); q != the request params' q: CC_ERR_LEN
+ * (gen_proof needs no params: q > CC_MAX_Q is CC_ERR_DECODE); k > q: CC_ERR_LEN; n > CC_MAX_BATCH:
+ * CC_ERR_DECODE.
+ * Scalars are reduced mod r, a bad prefix or an off-curve elgamal_pk or h decodes to the identity, an
+ * identity result (k_i = 0, all blindings 0) is written as the identity encoding; nothing is rejected
+ * that the reference would not reject.
+ * The *_device forms take device pointers, are asynchronous on `stream` (NULL: the context stream) and
+ * take no concurrency slot: they first wait for the slots' batches.  A device set forwards to its first
+ * device.  (The 2^-4096 event of compute_h's try-and-increment giving up is CC_ERR_DECODE from the host
+ * form of new; the device form does not report it.)
+ * Secrets: the host forms copy msgs, rand, blind and elgamal_sk to the device and build the digits of
+ * k_i, m_i, b2_i and hb_i in device scratch; they overwrite those device copies with zeros before
+ * returning.  The *_device forms read the caller's buffers in place; their scratch (those digits) stays
+ * until the next call overwrites it or the context is destroyed. */
+cc_status cc_set_request_params(cc_ctx* ctx, size_t q, const uint8_t* g, const uint8_t* h, int table_bits);
+cc_status cc_sigreq_new_batch(cc_ctx* ctx, size_t n, size_t q, size_t k, const uint8_t* msgs,
+                              const uint8_t* elgamal_pk, const uint8_t* rand, uint8_t* out_commitment,
+                              uint8_t* out_h, uint8_t* out_ciphertexts);
+cc_status cc_sigreq_new_batch_device(cc_ctx* ctx, size_t n, size_t q, size_t k, const uint8_t* d_msgs,
+                                     const uint8_t* d_elgamal_pk, const uint8_t* d_rand, uint8_t* d_out_commitment,
+                                     uint8_t* d_out_h, uint8_t* d_out_ciphertexts, void* stream);
+cc_status cc_sigreq_pok_init_batch(cc_ctx* ctx, size_t n, size_t q, size_t k, const uint8_t* h,
+                                   const uint8_t* elgamal_pk, const uint8_t* blind, uint8_t* out_proofs);
+cc_status cc_sigreq_pok_init_batch_device(cc_ctx* ctx, size_t n, size_t q, size_t k, const uint8_t* d_h,
+                                          const uint8_t* d_elgamal_pk, const uint8_t* d_blind, uint8_t* d_out_proofs,
+                                          void* stream);
+cc_status cc_sigreq_pok_gen_proof_batch(cc_ctx* ctx, size_t n, size_t q, size_t k, const uint8_t* msgs,
+                                        const uint8_t* rand, const uint8_t* blind, const uint8_t* elgamal_sk,
+                                        const uint8_t* chal, uint8_t* proofs);
+cc_status cc_sigreq_pok_gen_proof_batch_device(cc_ctx* ctx, size_t n, size_t q, size_t k, const uint8_t* d_msgs,
+                                               const uint8_t* d_rand, const uint8_t* d_blind,
+                                               const uint8_t* d_elgamal_sk, const uint8_t* d_chal, uint8_t* d_proofs,
+                                               void* stream);
 
 /* Pedersen VSS share verification (secret_sharing PedersenVSS::verify_share,
  * used by trusted_party_PVSS_keygen, reference keygen.rs:74-122, 334-349), n shares in G1:

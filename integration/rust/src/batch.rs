@@ -262,5 +262,73 @@ pub fn unblind_batch(blind: &[BlindSignature], sks: &[FieldElement], ctx: &HipCt
         sigma_1: b.h.clone(), sigma_2: SignatureGroup::from_bytes(&out[i * sb..(i + 1) * sb]).unwrap() }).collect()
 }
 
+/// One prepared signature request: the request itself, the randomness `SignatureRequest::new` returns
+/// (r, k_0 ..), the serialized SignatureRequestProof record `cc_sigreq_verify_batch` reads, and its
+/// challenge.
+pub type PreparedRequest = (SignatureRequest, Vec<FieldElement>, Vec<u8>, FieldElement);
+
+/// SignatureRequest::new + SignatureRequestPoK::init / gen_proof (signature.rs:124-320) for n holders,
+/// each hiding the first k of its q messages under its own ElGamal key: fresh r, k_i and blindings per
+/// request (FieldElement::random), every commitment, ciphertext and Schnorr commitment on the GPU, the
+/// challenge as the reference derives it (from_msg_hash of SignatureRequestPoK::to_bytes), the responses
+/// on the GPU.
+pub fn sigreq_prove_batch(messages: &[Vec<FieldElement>], k: usize, elgamal_pks: &[SignatureGroup],
+                          elgamal_sks: &[FieldElement], params: &Params, ctx: &HipCtx) -> Vec<PreparedRequest> {
+    let (n, q) = (messages.len(), params.h.len());
+    if n == 0 { return Vec::new(); }
+    let sb = ctx.sig_bytes();
+    let gb = params.g.to_bytes();
+    let hb: Vec<u8> = params.h.iter().flat_map(|p| p.to_bytes()).collect();
+    assert_eq!(params.h.len(), q, "one h per message");  // len-guard
+    assert!(q > 0 && k <= q, "k hidden of q messages");  // len-guard
+    assert!(gb.len() == sb && hb.len() == q * sb, "params encodings");  // len-guard
+    ctx.check(unsafe { cc_set_request_params(ctx.raw, q, gb.as_ptr(), hb.as_ptr(), 0) });
+    assert!(messages.iter().all(|m| m.len() == q), "Params valid for {} messages", q);  // len-guard
+    assert_eq!(elgamal_pks.len(), n, "one ElGamal public key per request");  // len-guard
+    assert_eq!(elgamal_sks.len(), n, "one ElGamal secret key per request");  // len-guard
+    let pb = unsafe { cc_sigreq_proof_bytes(ctx.raw, k) };
+    let m: Vec<u8> = messages.iter().flatten().flat_map(|f| f.to_bytes()).collect();
+    let pk: Vec<u8> = elgamal_pks.iter().flat_map(|p| p.to_bytes()).collect();
+    let rand: Vec<u8> = (0..n * (k + 1)).flat_map(|_| FieldElement::random().to_bytes()).collect();
+    assert!(m.len() == n * q * 48 && pk.len() == n * sb, "message and key encodings");  // len-guard
+    assert!(rand.len() == n * (k + 1) * 48, "randomness encodings");  // len-guard
+    let (mut cm, mut h, mut ct) = (vec![0u8; n * sb], vec![0u8; n * sb], vec![0u8; n * k * 2 * sb]);
+    ctx.check(unsafe { cc_sigreq_new_batch(ctx.raw, n, q, k, m.as_ptr(), pk.as_ptr(), rand.as_ptr(),
+                                           cm.as_mut_ptr(), h.as_mut_ptr(), ct.as_mut_ptr()) });
+    let blind: Vec<u8> = (0..n * (3 * k + 2)).flat_map(|_| FieldElement::random().to_bytes()).collect();
+    let mut proofs = vec![0u8; n * pb];
+    assert!(blind.len() == n * (3 * k + 2) * 48, "blinding encodings");  // len-guard
+    assert!(h.len() == n * sb && proofs.len() == n * pb, "h and proof records");  // len-guard
+    ctx.check(unsafe { cc_sigreq_pok_init_batch(ctx.raw, n, q, k, h.as_ptr(), pk.as_ptr(), blind.as_ptr(),
+                                                proofs.as_mut_ptr()) });
+    // to_bytes: g | T_sk | h_0 .. h_{k-1} | g | T_comm | k x (g | T_1i | pk | h | T_2i)
+    let chals: Vec<FieldElement> = (0..n).map(|i| {
+        let p = &proofs[i * pb..(i + 1) * pb];
+        let mut row = [&gb[..], &p[..sb], &hb[..k * sb], &gb[..], &p[sb + 48..2 * sb + 48]].concat();
+        for j in 0..k {
+            let o = 2 * sb + 48 * (k + 2) + j * (2 * sb + 144);
+            row.extend_from_slice(&[&gb[..], &p[o..o + sb], &pk[i * sb..(i + 1) * sb], &h[i * sb..(i + 1) * sb],
+                                    &p[o + sb + 48..o + 2 * sb + 48]].concat());
+        }
+        FieldElement::from_msg_hash(&row)
+    }).collect();
+    let sk: Vec<u8> = elgamal_sks.iter().flat_map(|s| s.to_bytes()).collect();
+    let ch: Vec<u8> = chals.iter().flat_map(|c| c.to_bytes()).collect();
+    assert!(sk.len() == n * 48 && ch.len() == n * 48, "key and challenge encodings");  // len-guard
+    ctx.check(unsafe { cc_sigreq_pok_gen_proof_batch(ctx.raw, n, q, k, m.as_ptr(), rand.as_ptr(), blind.as_ptr(),
+                                                     sk.as_ptr(), ch.as_ptr(), proofs.as_mut_ptr()) });
+    let pt = |b: &[u8]| SignatureGroup::from_bytes(b).unwrap();
+    chals.into_iter().enumerate().map(|(i, c)| {
+        let req = SignatureRequest {
+            known_messages: messages[i][k..].to_vec().into(),
+            commitment: pt(&cm[i * sb..(i + 1) * sb]),
+            ciphertexts: (0..k).map(|j| { let o = (i * k + j) * 2 * sb; (pt(&ct[o..o + sb]), pt(&ct[o + sb..o + 2 * sb])) })
+                .collect() };
+        let rs = (0..k + 1).map(|j| FieldElement::from_bytes(&rand[(i * (k + 1) + j) * 48..(i * (k + 1) + j + 1) * 48])
+                                .unwrap()).collect();
+        (req, rs, proofs[i * pb..(i + 1) * pb].to_vec(), c)
+    }).collect()
+}
+
 #[allow(dead_code)]
 const _MODE_TYPE: c_int = CC_SIG_G2;

@@ -92,6 +92,25 @@ extern "C" {
                                          d_chal: *const u8, d_out_responses: *mut u8, stream: *mut c_void) -> c_int;
     pub fn cc_unblind_batch(ctx: *mut CcCtx, n: usize, c1: *const u8, c2: *const u8, sk: *const u8,
                             out_sigma2: *mut u8) -> c_int;
+    // holder side of issuance: SignatureRequest::new and SignatureRequestPoK::init / gen_proof
+    pub fn cc_set_request_params(ctx: *mut CcCtx, q: usize, g: *const u8, h: *const u8, table_bits: c_int) -> c_int;
+    pub fn cc_sigreq_new_batch(ctx: *mut CcCtx, n: usize, q: usize, k: usize, msgs: *const u8,
+                               elgamal_pk: *const u8, rand: *const u8, out_commitment: *mut u8, out_h: *mut u8,
+                               out_ciphertexts: *mut u8) -> c_int;
+    pub fn cc_sigreq_new_batch_device(ctx: *mut CcCtx, n: usize, q: usize, k: usize, d_msgs: *const u8,
+                                      d_elgamal_pk: *const u8, d_rand: *const u8, d_out_commitment: *mut u8,
+                                      d_out_h: *mut u8, d_out_ciphertexts: *mut u8, stream: *mut c_void) -> c_int;
+    pub fn cc_sigreq_pok_init_batch(ctx: *mut CcCtx, n: usize, q: usize, k: usize, h: *const u8,
+                                    elgamal_pk: *const u8, blind: *const u8, out_proofs: *mut u8) -> c_int;
+    pub fn cc_sigreq_pok_init_batch_device(ctx: *mut CcCtx, n: usize, q: usize, k: usize, d_h: *const u8,
+                                           d_elgamal_pk: *const u8, d_blind: *const u8, d_out_proofs: *mut u8,
+                                           stream: *mut c_void) -> c_int;
+    pub fn cc_sigreq_pok_gen_proof_batch(ctx: *mut CcCtx, n: usize, q: usize, k: usize, msgs: *const u8,
+                                         rand: *const u8, blind: *const u8, elgamal_sk: *const u8,
+                                         chal: *const u8, proofs: *mut u8) -> c_int;
+    pub fn cc_sigreq_pok_gen_proof_batch_device(ctx: *mut CcCtx, n: usize, q: usize, k: usize, d_msgs: *const u8,
+                                                d_rand: *const u8, d_blind: *const u8, d_elgamal_sk: *const u8,
+                                                d_chal: *const u8, d_proofs: *mut u8, stream: *mut c_void) -> c_int;
     // RLC batch mode for PoK proofs: the partial (finished by cc_rlc_finish_device) and the host form
     pub fn cc_pok_rlc_partial_device(ctx: *mut CcCtx, n: usize, q: usize, r: usize, nresp: usize, base_index: u64,
                                      seed32: *const u8, d_sigma1: *const u8, d_sigma2: *const u8, d_j: *const u8,
