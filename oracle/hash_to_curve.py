@@ -101,6 +101,67 @@ def g2_from_msg_hash(msg: bytes):
     return G.add(G.add(t3, t1), t2)
 
 
+# ---------------------------------------------------------------- the same walks, with a record of the branches
+def f2_sqrt_amcl_traced(x):
+    """(f2_sqrt_amcl(x), branch): 'zero' (x = 0), 'norm' (a^2 + b^2 is not a square), 'first' (the root comes
+    from (a + w) / 2), 'second' (from (a - w) / 2), 'halves' (neither half-sum is a square)."""
+    a, b = x
+    if a % P == 0 and b % P == 0:
+        return (0, 0), "zero"
+    w1 = (b * b + a * a) % P
+    if not fp_is_qr(w1):
+        return None, "norm"
+    w1 = fp_sqrt_amcl(w1)
+    inv2 = (P + 1) // 2
+    w2, branch = (a + w1) * inv2 % P, "first"
+    if not fp_is_qr(w2):
+        w2, branch = (a - w1) * inv2 % P, "second"
+        if not fp_is_qr(w2):
+            return None, "halves"
+    s = fp_sqrt_amcl(w2)
+    return (s, b * pow(2 * s, P - 2, P) % P), branch
+
+
+def mapit_trace(msg: bytes, clear_cofactor=True):
+    """The branches g1_from_msg_hash and g2_from_msg_hash take on msg:
+    dict(reductions: subtractions of p that bring the 48-byte digest below p,
+         g1_tries: index of the first x with a square x^3 + 4, g1_negated: the root's integer value was odd,
+         g2_tries: index of the first x whose 1 + x i gives a square, g2_rejects: the failed tries' branches of
+         f2_sqrt_amcl_traced, g2_root: the successful try's, wrapped: an increment passed p - 1),
+    and, with clear_cofactor, the two points as (g1, g2)."""
+    d = int.from_bytes(hash_msg(msg), "big")
+    tr = {"reductions": d // P}
+    x0 = d % P
+    x, t = x0, 0
+    while not fp_is_qr((x * x * x + 4) % P):
+        x, t = (x + 1) % P, t + 1
+    y = fp_sqrt_amcl((x * x * x + 4) % P)
+    tr["g1_tries"], tr["g1_negated"] = t, bool(y & 1)
+    if y & 1:
+        y = (P - y) % P
+    g1 = (x, y)
+    wrapped = x < x0
+    x, t, rejects = x0, 0, []
+    while True:
+        X2 = (1, x)
+        y2, branch = f2_sqrt_amcl_traced(B.f2_add(B.f2_mul(B.f2_mul(X2, X2), X2), B.B2))
+        if y2 is not None:
+            break
+        rejects.append(branch)
+        x, t = (x + 1) % P, t + 1
+    tr["g2_tries"], tr["g2_rejects"], tr["g2_root"], tr["wrapped"] = t, rejects, branch, wrapped or x < x0
+    if not clear_cofactor:
+        return tr, None, None
+    G = B.G2
+    Q = (X2, y2)
+    xQ = _mul_signed(G, Q, X)
+    x2Q = _mul_signed(G, xQ, X)
+    t1 = G.add(G.add(x2Q, G.neg(xQ)), G.neg(Q))
+    t2 = S.psi(G.add(xQ, G.neg(Q)))
+    t3 = S.psi(S.psi(G.dbl(Q)))
+    return tr, B.G1.mul_any(g1, H1), G.add(G.add(t3, t1), t2)
+
+
 def params_new(grp_mode: str, msg_count: int, label: bytes):
     """Params::new (src/signature.rs:22-32): (g, g_tilde, h[]) with SignatureGroup = G2 under SigG2."""
     sig = g2_from_msg_hash if grp_mode == "G2" else g1_from_msg_hash

@@ -414,6 +414,71 @@ def make_hash_to_curve():
     return out
 
 
+H2C_CLASSES = ("reductions_0", "reductions_mid", "reductions_9", "g1_try_0", "g1_try_1", "g1_try_2", "g1_try_4_plus",
+               "g1_root_kept", "g1_root_negated", "g2_try_0", "g2_try_1", "g2_try_2", "g2_try_4_plus",
+               "g2_reject_norm", "g2_root_first", "g2_root_second")
+H2C_LENGTHS = [97 + 48 * j for j in range(4)] + [192 + 48 * j for j in range(4)] + [407, 408, 409, 1000]
+
+
+def h2c_classes(tr):
+    """The classes of H2C_CLASSES a trace of oracle/hash_to_curve.py mapit_trace belongs to."""
+    def tries(t):
+        return str(t) if t <= 2 else "4_plus" if t >= 4 else None
+    out = {"reductions_0" if tr["reductions"] == 0 else "reductions_9" if tr["reductions"] == 9 else "reductions_mid",
+           "g1_root_negated" if tr["g1_negated"] else "g1_root_kept", f"g2_root_{tr['g2_root']}"}
+    if tries(tr["g1_tries"]):
+        out.add(f"g1_try_{tries(tr['g1_tries'])}")
+    if tries(tr["g2_tries"]):
+        out.add(f"g2_try_{tries(tr['g2_tries'])}")
+    if "norm" in tr["g2_rejects"]:
+        out.add("g2_reject_norm")
+    return out
+
+
+def make_hash_to_curve_edges(seed=b"h2c-edges"):
+    """from_msg_hash by branch (PARITY UNPINNED, as make_hash_to_curve): seeded counter messages, searched
+    with the traced mapit of oracle/hash_to_curve.py, the first message kept for every class of H2C_CLASSES:
+    the reduction of the 48-byte digest mod p in zero, nine (the most: 2^384 < 10 p) and some number in
+    between of subtractions; G1's first square x^3 + 4 at try 0, 1, 2 and >= 4, its root kept and negated
+    (odd integer value); G2's first success at try 0, 1, 2 and >= 4, a rejection because the norm is not a
+    square (the other rejection, neither half-sum a square, cannot occur: w^2 = a^2 + b^2 makes the product
+    of the two half-sums -b^2 / 4, which is no square as -1 is none, so exactly one of them is), the root from the
+    first half-sum (a + w) / 2 and from the second (a - w) / 2.  Then one message of every length of
+    H2C_LENGTHS: the rows compute_h hashes (97 + 48 j and 192 + 48 j bytes), three full SHAKE256 blocks and
+    either side, and 1000 bytes.
+
+    NO DIGEST SEARCH REACHES: x^3 + b = 0 (one x in p); the increment wrapping past p - 1 (the digest mod p
+    would have to lie within a few units of p); a zero Fp2 argument to the square root (X^3 = -4 (1 + i) for
+    X = 1 + x i); the identity after cofactor clearing; 4096 failed tries (probability 2^-4096)."""
+    from oracle import hash_to_curve as H
+    import hashlib
+
+    def record(m, classes):
+        tr, g1, g2 = H.mapit_trace(m)
+        return {"msg": hx(m), "shake256_48": hashlib.shake_256(m).hexdigest(48), "g1": hx(B.g1_to_bytes(g1)),
+                "g2": hx(B.g2_to_bytes(g2)), "trace": tr, "classes": sorted(classes)}
+
+    found, ctr = {}, 0
+    while len(found) < len(H2C_CLASSES):
+        m = seed + b"/%d/" % ctr + bytes((ctr * 37 + i) & 0xFF for i in range(ctr % 61))  # lengths differ
+        ctr += 1
+        tr, _, _ = H.mapit_trace(m, clear_cofactor=False)
+        assert not tr["wrapped"] and "halves" not in tr["g2_rejects"] and tr["g2_root"] != "zero"
+        new = [c for c in h2c_classes(tr) if c not in found]
+        for c in new:
+            found[c] = m
+    msgs = []
+    for c in H2C_CLASSES:
+        if found[c] not in msgs:
+            msgs.append(found[c])
+    out = [record(m, [c for c in H2C_CLASSES if found[c] == m]) for m in msgs]
+    for n in H2C_LENGTHS:
+        out.append(record(hashlib.shake_256(seed + b"/len/%d" % n).digest(n), [f"length_{n}"]))
+    print(f"  h2c edges: {len(msgs)} messages for {len(H2C_CLASSES)} classes after {ctr} tries, "
+          f"{len(H2C_LENGTHS)} by length", flush=True)
+    return {"seed": hx(seed), "messages": out}
+
+
 ISSUE_KINDS = ["valid", "bad_sk_response", "bad_comm_response", "resp_mismatch", "bad_ct_proof", "wrong_chal", "valid"]
 
 
@@ -538,6 +603,8 @@ def main():
                                                               make_issuance(mode, 3, 3, 3, 23)]})
     if want("h2c"):
         write("hash_to_curve.json", make_hash_to_curve())
+    if want("h2cedges"):
+        write("hash_to_curve_edges.json", make_hash_to_curve_edges())
     if want("subgroup"):
         write("subgroup.json", make_subgroup(13))
     if want("torsion"):
