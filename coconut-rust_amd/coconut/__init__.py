@@ -17,4 +17,4 @@ from .dist import DeviceEngine, PokDeviceEngine  # noqa: F401
 from .issuance import (blind_sign_batch, sigreq_verify_batch, vss_verify_batch, unblind_batch,  # noqa: F401
                        SignatureRequest, SignatureRequestPoK, sigreq_new_batch, sigreq_pok_init_batch,
                        sigreq_pok_gen_proof_batch, sigreq_pok_to_bytes_batch, sigreq_challenge_batch,
-                       sigreq_proof_bytes)
+                       sigreq_proof_bytes, sigreq_verify_batch_device, blind_sign_batch_device)

@@ -65,6 +65,76 @@ def sigreq_verify_batch(ctx: Context, q: int, k: int, g: bytes, h: Sequence[byte
     return v[:n]
 
 
+def _dev_need(checks):
+    """need() for device tensors, [(tensor or None, bytes the call reads, name)]: each torch.uint8 and
+    contiguous, every length first, then every tensor the call reads on a GPU."""
+    for t, nbytes, what in checks:
+        if t is None:
+            need(None, nbytes, what)
+        elif str(t.dtype) != "torch.uint8" or not t.is_contiguous():
+            raise CoconutError(-4, f"{what}: a contiguous torch.uint8 tensor is required")
+        elif nbytes > 0 and t.numel() < nbytes:
+            raise CoconutError(-4, f"{what}: {t.numel()} bytes, the call reads {nbytes}")
+    for t, nbytes, what in checks:
+        if t is not None and nbytes > 0 and not t.is_cuda:
+            raise CoconutError(-4, f"{what}: a device tensor is required")
+
+
+def _dev_ptr(t):
+    return None if t is None or t.numel() == 0 else ctypes.c_void_p(t.data_ptr())
+
+
+def _stream_ptr(stream):
+    return None if stream is None else ctypes.c_void_p(stream.cuda_stream)
+
+
+def sigreq_verify_batch_device(ctx: Context, n: int, q: int, k: int, commitments, known, ciphertexts, elgamal_pks,
+                               proofs, chals, want_h: bool = False, stream=None):
+    """SignatureRequestProof::verify for n requests whose inputs are torch.uint8 CUDA tensors in the layouts
+    of sigreq_verify_batch (cc_sigreq_verify_batch_device), against the context's request params
+    (Context.set_request_params): g and h_0 .. h_{k-1} come from there.  Asynchronous on `stream` (a
+    torch.cuda.Stream; None: the context's).  Returns the verdict tensor (n bytes), or (verdicts, h) with
+    want_h: h = compute_h(commitment, known) of every request, what blind_sign_batch_device takes."""
+    import torch
+    sb = ctx.mode.sig_bytes
+    pb = sigreq_proof_bytes(ctx, k)
+    _dev_need(((commitments, n * sb, "commitments"), (known, n * max(q - k, 0) * 48, "known messages"),
+               (ciphertexts, n * k * 2 * sb, "ciphertexts"), (elgamal_pks, n * sb, "ElGamal keys"),
+               (proofs, n * pb, "proofs"), (chals, n * 48, "challenges")))
+    dev = commitments.device if n else None
+    v = torch.empty(n, dtype=torch.uint8, device=dev)  # no fill kernel: it would run on another stream
+    h = torch.empty(n * sb, dtype=torch.uint8, device=dev) if want_h else None
+    check(lib.cc_sigreq_verify_batch_device(ctx.h, n, q, k, _dev_ptr(commitments), _dev_ptr(known),
+                                            _dev_ptr(ciphertexts), _dev_ptr(elgamal_pks), _dev_ptr(proofs),
+                                            _dev_ptr(chals), _dev_ptr(v), _dev_ptr(h), _stream_ptr(stream)),
+          "cc_sigreq_verify_batch_device")
+    return (v, h) if want_h else v
+
+
+def blind_sign_batch_device(ctx: Context, n: int, q: int, k: int, commitments, known, ciphertexts, x: bytes,
+                            y: Sequence[bytes], h=None, stream=None):
+    """BlindSignature::new for n requests in HBM (cc_blind_sign_batch_device): torch.uint8 CUDA tensors in the
+    layouts of blind_sign_batch, the issuer's key x, y as host bytes.  h: the tensor sigreq_verify_batch_device
+    returned with want_h (None: h is hashed here; commitments may be None when h is given).  Asynchronous on
+    `stream`.  Returns the tensors (h, c~1, c~2), n encodings each."""
+    import torch
+    sb = ctx.mode.sig_bytes
+    yb = b"".join(y)
+    need(x, 48, "x")
+    need(yb, q * 48, "y")
+    _dev_need(((commitments, 0 if h is not None else n * sb, "commitments"),
+               (known, n * max(q - k, 0) * 48, "known messages"), (ciphertexts, n * k * 2 * sb, "ciphertexts"),
+               (h, n * sb if h is not None else 0, "h")))
+    src = h if h is not None else commitments
+    dev = src.device if n else None
+    outs = [torch.empty(n * sb, dtype=torch.uint8, device=dev) for _ in range(3)]
+    keep = [buf(bytes(x)), buf(yb)]
+    check(lib.cc_blind_sign_batch_device(ctx.h, n, q, k, _dev_ptr(commitments), _dev_ptr(known), _dev_ptr(ciphertexts),
+                                         _dev_ptr(h), keep[0][0], keep[1][0], *[_dev_ptr(o) for o in outs],
+                                         _stream_ptr(stream)), "cc_blind_sign_batch_device")
+    return tuple(outs)
+
+
 def vss_verify_batch(ctx: Context, t: int, g: bytes, h: bytes, commitment_sets: Sequence[Sequence[bytes]],
                      set_of: Sequence[int], ids: Sequence[int], shares: Sequence[tuple]) -> np.ndarray:
     """PedersenVSS::verify_share for a batch of (id, (s, s')) against their dealer's commitments (G1)."""

@@ -125,6 +125,16 @@ int cck_rq_two_base(int group, size_t n, int q, int k, int init, const uint8_t* 
                     hipStream_t st);
 int cck_rq_h_rows(int group, size_t n, int q, int k, const uint8_t* d_commitment, const uint8_t* d_msgs,
                   uint8_t* d_data, uint64_t* d_offsets, hipStream_t st);
+size_t cck_iv_table_words(int group, size_t n, int k);
+size_t cck_iv_cdig_bytes(size_t n);
+size_t cck_iv_dig_bytes(size_t n, int k);
+size_t cck_iv_ok_bytes(size_t n, int k);
+int cck_iv_checks(int group, size_t n, int q, int k, const uint8_t* d_comm, const uint8_t* d_cts, const uint8_t* d_pk,
+                  const uint8_t* d_proof, const uint8_t* d_chal, const uint8_t* d_h, const uint32_t* d_table,
+                  int wbits, const uint32_t* d_binf, uint32_t* d_tab, int8_t* d_cdig, int8_t* d_digs, uint8_t* d_ok,
+                  hipStream_t st);
+int cck_sigreq_combine(int group, size_t n, int k, const uint8_t* d_proof, const uint8_t* d_ok, uint8_t* d_verdicts,
+                       hipStream_t st);
 int cck_rq_responses(int group, size_t n, int q, int k, const uint8_t* d_msgs, const uint8_t* d_rnd,
                      const uint8_t* d_blind, const uint8_t* d_sk, const uint8_t* d_chal, uint8_t* d_proofs,
                      hipStream_t st);
@@ -290,6 +300,10 @@ struct cc_ctx {
     // their workspaces: per-request (pk, h) window tables, the two-base tasks' digits, compute_h's input
     // rows, offsets and failure flag
     DevBuf rq_tab, rq_dig, rq_hdata, rq_hoff, rq_fail;
+    // issuer side, device forms (issue_dev.hip): h where the caller takes none, the per-request tables of the
+    // variable bases, challenge and response digits, check flags; blind signing's Straus bases, scalars,
+    // interleaved outputs and the device copy of x | y
+    DevBuf iv_h, iv_tab, iv_cdig, iv_dig, iv_ok, bs_pts, bs_sc, bs_out, bs_xy;
     int n_simd = 0;  // SIMDs of the device (4 a CU), read once (pok_rlc_twin)
     // issuer table (cc_set_issuers): sorted ids, decoded verkeys, per-base 8-bit window tables
     size_t iss_n = 0, iss_q = 0;
@@ -494,7 +508,8 @@ cc_status cc_ctx_destroy(cc_ctx* c) {
                       &c->rlc_pts, &c->rlc_dig, &c->rlc_work, &c->rlc_pw, &c->rlc_finf,
                       &c->iss_ids, &c->iss_aff, &c->iss_inf, &c->iss_table, &c->agg_scratch, &c->dev_err,
                       &c->prove_idx, &c->prove_scratch, &c->rq_aff, &c->rq_inf, &c->rq_table, &c->rq_tab, &c->rq_dig,
-                      &c->rq_hdata, &c->rq_hoff, &c->rq_fail};
+                      &c->rq_hdata, &c->rq_hoff, &c->rq_fail, &c->iv_h, &c->iv_tab, &c->iv_cdig, &c->iv_dig, &c->iv_ok,
+                      &c->bs_pts, &c->bs_sc, &c->bs_out, &c->bs_xy};
     for (auto* b : bufs) b->release();
     for (auto& b : c->in_aux) b.release();
     for (auto& e : c->ev) if (e) (void)hipEventDestroy(e);
@@ -2505,6 +2520,110 @@ cc_status cc_sigreq_pok_gen_proof_batch(cc_ctx* c, size_t n, size_t q, size_t k,
                  hipMemsetAsync(dK.p, 0, n * 48, st) == hipSuccess;
     if (k) wiped = hipMemsetAsync(c->in_msgs.p, 0, mb, st) == hipSuccess && wiped;
     if (hipStreamSynchronize(st) != hipSuccess || !wiped) return s ? s : CC_ERR_HIP;
+    return s;
+}
+
+// ---------------------------------------------------------------- issuer side, device forms (issue_dev.hip)
+// h = compute_h(commitment, known) as compute_h_batch computes it, rows built on the device.  The one-in-
+// 2^4096 failure of the hash is not reported (as cc_sigreq_new_batch_device).
+static cc_status launch_issuer_h(cc_ctx* c, size_t n, size_t q, size_t k, const uint8_t* d_comm, const uint8_t* d_known,
+                                 uint8_t* d_h, hipStream_t st) {
+    const int sg = sig_group(c->mode);
+    const size_t kn = q - k, len = (size_t)sig_bytes(c->mode) + 48 * kn;
+    if (c->rq_hdata.ensure(n * len + 16) || c->rq_hoff.ensure((n + 1) * 8) || c->rq_fail.ensure(4)) return CC_ERR_HIP;
+    // the known messages are the rows' only messages: q - k of them, none hidden
+    KCK(cck_rq_h_rows(sg, n, (int)kn, 0, d_comm, d_known, c->rq_hdata.as<uint8_t>(), c->rq_hoff.as<uint64_t>(), st));
+    HIPCK(hipMemsetAsync(c->rq_fail.p, 0, 4, st));
+    KCK(cck_h_input_canon(sg, n, len, (int)kn, c->rq_hdata.as<uint8_t>(), st));
+    KCK(cck_hash_to_curve(sg, n, c->rq_hdata.as<uint8_t>(), c->rq_hoff.as<uint64_t>(), d_h, c->rq_fail.as<uint32_t>(),
+                          st));
+    return CC_OK;
+}
+
+cc_status cc_sigreq_verify_batch_device(cc_ctx* c, size_t n, size_t q, size_t k, const uint8_t* d_commitment,
+                                        const uint8_t* d_known, const uint8_t* d_ciphertexts,
+                                        const uint8_t* d_elgamal_pk, const uint8_t* d_proofs, const uint8_t* d_chal,
+                                        uint8_t* d_verdicts, uint8_t* d_out_h, void* stream) {
+    c = primary(c);  // a device set forwards to its first device
+    if (!c || (n && (!d_commitment || !d_elgamal_pk || !d_proofs || !d_chal || !d_verdicts || (k && !d_ciphertexts) ||
+                     (q > k && !d_known))))
+        return CC_ERR_DECODE;
+    cc_status s = rq_checks(c, true, n, q, k);
+    if (s) return s;
+    if (!n) return CC_OK;
+    HIPCK(hipSetDevice(c->device));
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    StreamOrder order(c, st);
+    const int sg = sig_group(c->mode);
+    if (!d_out_h) {
+        if (c->iv_h.ensure(n * (size_t)sig_bytes(c->mode))) return CC_ERR_HIP;
+        d_out_h = c->iv_h.as<uint8_t>();
+    }
+    if (c->iv_tab.ensure(cck_iv_table_words(sg, n, (int)k) * 4) || c->iv_cdig.ensure(cck_iv_cdig_bytes(n)) ||
+        c->iv_dig.ensure(cck_iv_dig_bytes(n, (int)k) + 16) || c->iv_ok.ensure(cck_iv_ok_bytes(n, (int)k)))
+        return CC_ERR_HIP;
+    s = launch_issuer_h(c, n, q, k, d_commitment, d_known, d_out_h, st);
+    if (s) return s;
+    KCK(cck_iv_checks(sg, n, (int)q, (int)k, d_commitment, d_ciphertexts, d_elgamal_pk, d_proofs, d_chal, d_out_h,
+                      c->rq_table.as<uint32_t>(), c->rq_wbits, c->rq_inf.as<uint32_t>(), c->iv_tab.as<uint32_t>(),
+                      c->iv_cdig.as<int8_t>(), c->iv_dig.as<int8_t>(), c->iv_ok.as<uint8_t>(), st));
+    KCK(cck_sigreq_combine(sg, n, (int)k, d_proofs, c->iv_ok.as<uint8_t>(), d_verdicts, st));
+    return CC_OK;
+}
+
+cc_status cc_blind_sign_batch_device(cc_ctx* c, size_t n, size_t q, size_t k, const uint8_t* d_commitment,
+                                     const uint8_t* d_known, const uint8_t* d_ciphertexts, const uint8_t* d_h,
+                                     const uint8_t* x, const uint8_t* y, uint8_t* d_out_h, uint8_t* d_out_c1,
+                                     uint8_t* d_out_c2, void* stream) {
+    c = primary(c);  // a device set forwards to its first device
+    if (!c || !x || (q && !y) ||
+        (n && ((!d_h && !d_commitment) || !d_out_h || !d_out_c1 || !d_out_c2 || (k && !d_ciphertexts) ||
+               (q > k && !d_known))))
+        return CC_ERR_DECODE;
+    cc_status s = rq_checks(c, false, n, q, k);
+    if (s) return s;
+    if (!n) return CC_OK;
+    HIPCK(hipSetDevice(c->device));
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    StreamOrder order(c, st);
+    const size_t sb = (size_t)sig_bytes(c->mode), t = k + 1, xyb = (q + 1) * 48;
+    const int sg = sig_group(c->mode);
+    if (c->bs_pts.ensure(2 * n * t * sb) || c->bs_sc.ensure(2 * n * t * 32) || c->bs_out.ensure(2 * n * sb) ||
+        c->bs_xy.ensure(xyb + 16))
+        return CC_ERR_HIP;
+    s = agg_scratch(c, sg, 2 * n, t);
+    if (s) return s;
+    const size_t scr = 2 * n * cck_straus_words(sg, t) * 4;
+    if (d_h) {
+        if (d_h != d_out_h) HIPCK(hipMemcpyAsync(d_out_h, d_h, n * sb, hipMemcpyDeviceToDevice, st));
+    } else {
+        s = launch_issuer_h(c, n, q, k, d_commitment, d_known, d_out_h, st);
+        if (s) return s;
+    }
+    auto run = [&]() -> cc_status {
+        // x | y through the pinned ring: the caller's arrays are free again when the call returns
+        std::vector<uint8_t> xy(xyb);
+        memcpy(xy.data(), x, 48);
+        if (q) memcpy(xy.data() + 48, y, q * 48);
+        const int up = c->stage[0].upload(c->bs_xy.p, xy.data(), xyb, st);
+        std::fill(xy.begin(), xy.end(), (uint8_t)0);
+        if (up) return CC_ERR_HIP;
+        KCK(cck_blind_assemble(sg, n, (int)q, (int)k, d_ciphertexts, d_out_h, d_known, c->bs_xy.as<uint8_t>(),
+                               c->bs_xy.as<uint8_t>() + 48, c->bs_pts.as<uint8_t>(), c->bs_sc.as<uint32_t>(), st));
+        KCK(cck_msm_straus(sg, 2 * n, t, c->bs_pts.as<uint8_t>(), t * sb, 0, sb, c->bs_sc.as<uint32_t>(), 1,
+                           c->agg_scratch.as<uint32_t>(), c->bs_out.as<uint8_t>(), st));
+        // tasks 2r / 2r + 1 -> c~1_r / c~2_r: strided device copies
+        KCK(cck_copy_rows(n, sb, c->bs_out.as<uint8_t>(), 2 * sb, d_out_c1, st));
+        KCK(cck_copy_rows(n, sb, c->bs_out.as<uint8_t>() + sb, 2 * sb, d_out_c2, st));
+        return CC_OK;
+    };
+    s = run();
+    // queued behind the work: the device copies of x | y, of the tasks' scalars (y_i, x + sum y m) and of
+    // their digits (the Straus scratch) are zeroed
+    const bool wiped = hipMemsetAsync(c->bs_xy.p, 0, xyb, st) == hipSuccess &&
+                       hipMemsetAsync(c->bs_sc.p, 0, 2 * n * t * 32, st) == hipSuccess &&
+                       hipMemsetAsync(c->agg_scratch.p, 0, scr, st) == hipSuccess;
+    if (!wiped) return s ? s : CC_ERR_HIP;
     return s;
 }
 

@@ -336,6 +336,15 @@ int cck_sigreq_verify(int group, size_t n, int k, const uint8_t* d_g, const uint
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
+// k_sigreq_combine alone, over check flags another kernel wrote (issue_dev.hip)
+int cck_sigreq_combine(int group, size_t n, int k, const uint8_t* d_proof, const uint8_t* d_ok, uint8_t* d_verdicts,
+                       hipStream_t st) {
+    if (!n) return 0;
+    hipLaunchKernelGGL(k_sigreq_combine, dim3(nblocks(n, 64)), dim3(64), 0, st, n, k, (size_t)(group == 1 ? 97 : 192),
+                       d_proof, d_ok, d_verdicts);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
 int cck_vss_verify(size_t n, int t, const uint8_t* d_g, const uint8_t* d_h, const uint8_t* d_comms,
                    const uint32_t* d_set_of, const uint64_t* d_ids, const uint8_t* d_shares, uint32_t* d_scratch,
                    uint8_t* d_ok, hipStream_t st) {

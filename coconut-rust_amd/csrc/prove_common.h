@@ -47,12 +47,13 @@ DEV void sp_fill_g2(uint32_t* ent, uint32_t* zs, uint32_t* pre, int h, int k, co
     }
 }
 
-// one inversion for the 16 entries, then walk back: z_e^-1 = inv * prefix_e; inv *= z_e
-DEV void sp_norm_g2(uint32_t* ent, const uint32_t* zs, const uint32_t* pre, int h, const lz::F2R& acc_z) {
+// one inversion for the ne entries (a two-base table: 16), then walk back: z_e^-1 = inv * prefix_e; inv *= z_e
+DEV void sp_norm_g2(uint32_t* ent, const uint32_t* zs, const uint32_t* pre, int h, const lz::F2R& acc_z,
+                    int ne = SP_ENT) {
     using namespace lz;
     F2R zinv = reduce(inv(acc_z));
 #pragma unroll 1
-    for (int e = SP_ENT - 1; e >= 0; e--) {
+    for (int e = ne - 1; e >= 0; e--) {
         uint32_t* w = ent + (e * 2 + h) * SEW;
         if (w[SEF]) continue;  // identity multiple (pair-uniform: both halves carry the flag)
         const F2R z = ld_w(zs + (e * 2 + h) * LN);
@@ -99,13 +100,13 @@ DEV void sp_fill_g1(uint32_t* ent, uint32_t* zs, uint32_t* pre, int k, const uin
     }
 }
 
-DEV void sp_norm_g1(uint32_t* ent, const uint32_t* zs, const uint32_t* pre, const lz::FR& acc_z) {
+DEV void sp_norm_g1(uint32_t* ent, const uint32_t* zs, const uint32_t* pre, const lz::FR& acc_z, int ne = SP_ENT) {
     using namespace lz;
     cc::Fp zinv_s;
     fp_inv(zinv_s, out_r(acc_z));
     FR zinv = reduce(in_r(zinv_s));
 #pragma unroll 1
-    for (int e = SP_ENT - 1; e >= 0; e--) {
+    for (int e = ne - 1; e >= 0; e--) {
         uint32_t* w = ent + e * SEW;
         if (w[SEF]) continue;  // identity multiple
         const FR z = ld_r1(zs + e * LN);

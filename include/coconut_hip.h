@@ -434,6 +434,42 @@ cc_status cc_sigreq_pok_gen_proof_batch_device(cc_ctx* ctx, size_t n, size_t q, 
                                                const uint8_t* d_elgamal_sk, const uint8_t* d_chal, uint8_t* d_proofs,
                                                void* stream);
 
+/* Issuer side of issuance with every input in HBM: the device forms of cc_sigreq_verify_batch and
+ * cc_blind_sign_batch (buffer layouts and the proof record as there), asynchronous on `stream` (NULL: the
+ * context stream), no host round trip.  They take no concurrency slot: they first wait for the slots'
+ * batches.  A device set forwards to its first device.
+ *
+ * cc_sigreq_verify_batch_device reads g and h_0 .. h_{k-1} from the context's request params
+ * (cc_set_request_params) and gives, per request, exactly the verdict of cc_sigreq_verify_batch called
+ * with those: the fixed-base terms r g, sum r_i h_i come from the request params' window tables with no
+ * doubling, the variable-base terms (c pk, c commitment, c c1_i, r_2a pk + r_2b h + c c2_i) from one
+ * per-request table of signed 4-bit windows (no endomorphism: a key or ciphertext outside the subgroup
+ * gives its integer multiple).  With d_out_h set it also writes h = compute_h(commitment, known) of every
+ * request, accepted or not: the bytes cc_blind_sign_batch returns in out_h.
+ *
+ * cc_blind_sign_batch_device gives the bytes of cc_blind_sign_batch.  With d_h set it takes h from there
+ * (what the verify wrote) instead of hashing again, and d_commitment may then be NULL; with d_h NULL it
+ * computes h from d_commitment and d_known.  Either way h is written to d_out_h (d_out_h == d_h is
+ * allowed).  It needs neither request params nor a verkey, only the context: compute_h is a hash, and the
+ * two sums run over each request's own ciphertexts.  x (48 B) and y (q x 48 B) are HOST arrays, one issuer
+ * key for the batch; the call copies them before it returns and queues, behind its work, the zeroing of
+ * its device copies of x, y, the tasks' scalars and their digits.
+ *
+ * Checks, in this order and before the n = 0 shortcut: NULL context (sign: NULL x, or NULL y with q > 0):
+ * CC_ERR_DECODE; a NULL buffer the call would read or write with n > 0 (k = 0: the ciphertexts may be
+ * NULL; q = k: known may be NULL; d_out_h of verify and d_h of sign are optional): CC_ERR_DECODE; verify:
+ * no request params: CC_ERR_STATE, q != the request params' q: CC_ERR_LEN (sign: q > CC_MAX_Q:
+ * CC_ERR_DECODE); k > q: CC_ERR_LEN; n > CC_MAX_BATCH: CC_ERR_DECODE; n = 0: CC_OK, nothing launched.
+ * The 2^-4096 event of compute_h giving up is not reported (as cc_sigreq_new_batch_device). */
+cc_status cc_sigreq_verify_batch_device(cc_ctx* ctx, size_t n, size_t q, size_t k, const uint8_t* d_commitment,
+                                        const uint8_t* d_known, const uint8_t* d_ciphertexts,
+                                        const uint8_t* d_elgamal_pk, const uint8_t* d_proofs, const uint8_t* d_chal,
+                                        uint8_t* d_verdicts, uint8_t* d_out_h_or_null, void* stream);
+cc_status cc_blind_sign_batch_device(cc_ctx* ctx, size_t n, size_t q, size_t k, const uint8_t* d_commitment,
+                                     const uint8_t* d_known, const uint8_t* d_ciphertexts, const uint8_t* d_h_or_null,
+                                     const uint8_t* x, const uint8_t* y, uint8_t* d_out_h, uint8_t* d_out_c1,
+                                     uint8_t* d_out_c2, void* stream);
+
 /* Pedersen VSS share verification (secret_sharing PedersenVSS::verify_share,
  * used by trusted_party_PVSS_keygen, reference keygen.rs:74-122, 334-349), n shares in G1:
  *   g * s + h * s' == sum_{k<t} id^k * C_k, C = commitments[set_of[i]] (n_sets x t x 97 B),

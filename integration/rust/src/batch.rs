@@ -330,5 +330,54 @@ pub fn sigreq_prove_batch(messages: &[Vec<FieldElement>], k: usize, elgamal_pks:
     }).collect()
 }
 
+/// A caller-owned buffer in HBM: its device address and its length in bytes.  The shim allocates no
+/// device memory; whoever does (a HIP binding, a tensor library) vouches for the pair once, here.
+#[derive(Clone, Copy)]
+pub struct DeviceBytes { ptr: *mut u8, len: usize }
+
+impl DeviceBytes {
+    /// Safety: `ptr` addresses `len` bytes of memory of the context's device, which stay allocated until
+    /// the stream the buffer is used on has run.
+    pub unsafe fn new(ptr: *mut u8, len: usize) -> DeviceBytes { DeviceBytes { ptr, len } }
+    pub fn len(&self) -> usize { self.len }
+    pub fn as_ptr(&self) -> *mut u8 { self.ptr }
+}
+
+/// The issuer's step for n requests resident in HBM (signature.rs:324-433): SignatureRequestProof::verify
+/// against the context's request params (cc_set_request_params with this `params`), then
+/// BlindSignature::new with the h the verify computed, both queued on `stream` (null: the context's)
+/// with no host round trip.  Buffers in the layouts of cc_sigreq_verify_batch / cc_blind_sign_batch;
+/// verdicts n bytes, h, c1, c2 n SignatureGroup encodings each.  Every request is signed: the caller
+/// reads the verdicts and drops the refused ones.
+pub fn issuer_verify_sign_device(n: usize, k: usize, commitment: DeviceBytes, known: DeviceBytes,
+                                 ciphertexts: DeviceBytes, elgamal_pk: DeviceBytes, proofs: DeviceBytes,
+                                 chal: DeviceBytes, verdicts: DeviceBytes, h: DeviceBytes, c1: DeviceBytes,
+                                 c2: DeviceBytes, sigkey: &Sigkey, params: &Params, ctx: &HipCtx,
+                                 stream: *mut std::os::raw::c_void) {
+    let q = params.h.len();
+    let sb = ctx.sig_bytes();
+    let gb = params.g.to_bytes();
+    let hb: Vec<u8> = params.h.iter().flat_map(|p| p.to_bytes()).collect();
+    assert!(q > 0 && k <= q, "k hidden of q messages");  // len-guard
+    assert_eq!(sigkey.y.len(), q, "Sigkey valid for {} messages", q);  // len-guard
+    assert!(gb.len() == sb && hb.len() == q * sb, "params encodings");  // len-guard
+    ctx.check(unsafe { cc_set_request_params(ctx.raw, q, gb.as_ptr(), hb.as_ptr(), 0) });
+    let pb = unsafe { cc_sigreq_proof_bytes(ctx.raw, k) };
+    assert!(commitment.len() >= n * sb && known.len() >= n * (q - k) * 48, "commitments and known messages");  // len-guard
+    assert!(ciphertexts.len() >= n * k * 2 * sb && elgamal_pk.len() >= n * sb, "ciphertexts and ElGamal keys");  // len-guard
+    assert!(proofs.len() >= n * pb && chal.len() >= n * 48, "proof records and challenges");  // len-guard
+    assert!(verdicts.len() >= n && h.len() >= n * sb, "verdicts and h");  // len-guard
+    assert!(c1.len() >= n * sb && c2.len() >= n * sb, "blind signature halves");  // len-guard
+    ctx.check(unsafe { cc_sigreq_verify_batch_device(ctx.raw, n, q, k, commitment.as_ptr(), known.as_ptr(),
+                                                     ciphertexts.as_ptr(), elgamal_pk.as_ptr(), proofs.as_ptr(),
+                                                     chal.as_ptr(), verdicts.as_ptr(), h.as_ptr(), stream) });
+    let x = sigkey.x.to_bytes();
+    let y: Vec<u8> = sigkey.y.iter().flat_map(|v| v.to_bytes()).collect();
+    assert!(x.len() == 48 && y.len() == q * 48, "signing key encodings");  // len-guard
+    ctx.check(unsafe { cc_blind_sign_batch_device(ctx.raw, n, q, k, commitment.as_ptr(), known.as_ptr(),
+                                                  ciphertexts.as_ptr(), h.as_ptr(), x.as_ptr(), y.as_ptr(),
+                                                  h.as_ptr(), c1.as_ptr(), c2.as_ptr(), stream) });
+}
+
 #[allow(dead_code)]
 const _MODE_TYPE: c_int = CC_SIG_G2;

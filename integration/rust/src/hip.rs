@@ -134,6 +134,15 @@ extern "C" {
                                   commitment: *const u8, known: *const u8, ciphertexts: *const u8,
                                   elgamal_pk: *const u8, proofs: *const u8, chal: *const u8,
                                   verdicts: *mut u8) -> c_int;
+    // issuer side with the inputs in HBM (x, y: host arrays)
+    pub fn cc_sigreq_verify_batch_device(ctx: *mut CcCtx, n: usize, q: usize, k: usize, d_commitment: *const u8,
+                                         d_known: *const u8, d_ciphertexts: *const u8, d_elgamal_pk: *const u8,
+                                         d_proofs: *const u8, d_chal: *const u8, d_verdicts: *mut u8,
+                                         d_out_h_or_null: *mut u8, stream: *mut c_void) -> c_int;
+    pub fn cc_blind_sign_batch_device(ctx: *mut CcCtx, n: usize, q: usize, k: usize, d_commitment: *const u8,
+                                      d_known: *const u8, d_ciphertexts: *const u8, d_h_or_null: *const u8,
+                                      x: *const u8, y: *const u8, d_out_h: *mut u8, d_out_c1: *mut u8,
+                                      d_out_c2: *mut u8, stream: *mut c_void) -> c_int;
     pub fn cc_vss_verify_batch(ctx: *mut CcCtx, n: usize, t: usize, g: *const u8, h: *const u8,
                                commitments: *const u8, n_sets: usize, set_of: *const u32, ids: *const u64,
                                shares: *const u8, verdicts: *mut u8) -> c_int;
