@@ -52,6 +52,10 @@ _SIGS = {
                                     c_p, c_p]),
     "cc_pok_verify_batch_device": (c_int, [c_p, c_sz, c_sz, c_sz, c_sz, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
                                            c_p, c_p, c_p]),
+    "cc_pok_verify_batch_pervk_device": (c_int, [c_p, c_sz, c_sz, c_sz, c_sz, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
+                                                 c_p, c_p, c_p, c_p, c_p]),
+    "cc_pok_verify_batch_pervk": (c_int, [c_p, c_sz, c_sz, c_sz, c_sz, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
+                                          c_p, c_p, c_p, c_p]),
     "cc_pok_rlc_partial_device": (c_int, [c_p, c_sz, c_sz, c_sz, c_sz, ctypes.c_uint64, c_p, c_p, c_p, c_p, c_p,
                                           c_p, c_p, c_p, c_p, c_p, c_p]),
     "cc_pok_verify_batch_rlc": (c_int, [c_p, c_sz, c_sz, c_sz, c_sz, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),

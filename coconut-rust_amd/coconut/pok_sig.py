@@ -41,26 +41,42 @@ class PoKOfSignatureProof:
 
 def pok_verify_batch(ctx: Context, n: int, q: int, revealed_idx, nresp: int, sigma1: bytes, sigma2: bytes,
                      J: bytes, T: bytes, responses: bytes, chal: bytes, revealed_msgs: bytes,
-                     want_gt: bool = False, rlc: bool = False):
+                     want_gt: bool = False, rlc: bool = False, vk=None):
     """Batch PoK verify against the context's params and shared verkey.
+
+    vk=(X_bytes, Y_bytes) checks proof i against ITS OWN verkey instead (cc_pok_verify_batch_pervk):
+    X_bytes n x OtherGroup, Y_bytes n x q x OtherGroup.  The context then needs its params only, and
+    revealed_idx may be in any order (revealed_msgs follow it).  There is no RLC form of it.
 
     rlc=True checks the whole batch with one random-linear-combination pairing product first
     (cc_pok_verify_batch_rlc) and falls back to the per-proof path on reject, so the verdicts are the
     same; it has no GT output."""
     if rlc and want_gt:
         raise ValueError("rlc=True has no per-proof GT output (want_gt=True)")
+    if rlc and vk is not None:
+        raise ValueError("rlc=True needs the shared verkey (vk=None)")
     r = len(revealed_idx)
     sb, ob = ctx.mode.sig_bytes, ctx.mode.other_bytes
     for v, nb, what in ((sigma1, n * sb, "sigma'_1"), (sigma2, n * sb, "sigma'_2"), (J, n * ob, "J"),
                         (T, n * ob, "commitment"), (responses, n * nresp * 48, "responses"),
                         (chal, n * 48, "challenges"), (revealed_msgs, n * r * 48, "revealed messages")):
         need(v, nb, what)
+    if vk is not None:
+        vk_X, vk_Y = vk
+        need(vk_X, n * ob, "verkey X~ (one per proof)")
+        need(vk_Y, n * q * ob, "verkey Y~ (q per proof)")
     idx = np.ascontiguousarray(np.asarray(revealed_idx, dtype=np.uint64)) if r else np.zeros(1, np.uint64)
     verdicts = np.zeros(max(n, 1), dtype=np.uint8)
     gts = np.zeros(max(n, 1) * GT_BYTES, dtype=np.uint8) if want_gt else None
     keep = [buf(x) for x in (sigma1, sigma2, J, T, responses, chal, revealed_msgs)]
     ptrs = [k[0] for k in keep]
-    if rlc:
+    if vk is not None:
+        kv = [buf(x) for x in (vk_X, vk_Y)]
+        st = lib.cc_pok_verify_batch_pervk(ctx.h, n, q, r, nresp, ptrs[0], ptrs[1], ptrs[2], ptrs[3], ptrs[4], ptrs[5],
+                                           ctypes.c_void_p(idx.ctypes.data), ptrs[6], kv[0][0], kv[1][0],
+                                           ctypes.c_void_p(verdicts.ctypes.data),
+                                           ctypes.c_void_p(gts.ctypes.data) if want_gt else None)
+    elif rlc:
         st = lib.cc_pok_verify_batch_rlc(ctx.h, n, q, r, nresp, ptrs[0], ptrs[1], ptrs[2], ptrs[3], ptrs[4], ptrs[5],
                                          ctypes.c_void_p(idx.ctypes.data), ptrs[6],
                                          ctypes.c_void_p(verdicts.ctypes.data))

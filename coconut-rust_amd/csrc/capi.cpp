@@ -105,6 +105,11 @@ int cck_prep_pok_wide(int mode, size_t n, int q, int r, const uint8_t* d_s1, con
                  const uint8_t* d_T, const uint8_t* d_resp, const uint8_t* d_chal, const uint8_t* d_rev_msgs,
                  const uint32_t* d_rev_idx, const uint32_t* d_Xaff, uint32_t Xinf, const uint32_t* d_table, int wbits,
                  const uint32_t* d_binf, uint32_t* d_prep, uint32_t* d_flags, uint32_t* d_jtab, hipStream_t st);
+size_t cck_prep_pok_var_words(int mode, size_t n, size_t q);
+int cck_prep_pok_var(int mode, size_t n, int q, int r, const uint8_t* d_s1, const uint8_t* d_s2, const uint8_t* d_J,
+                     const uint8_t* d_T, const uint8_t* d_resp, const uint8_t* d_chal, const uint8_t* d_rev_msgs,
+                     const uint32_t* d_rev_idx, const uint8_t* d_vkX, const uint8_t* d_vkY, const uint32_t* d_gaff,
+                     uint32_t ginf, uint32_t* d_scratch, uint32_t* d_prep, uint32_t* d_flags, hipStream_t st);
 size_t cck_sigma_prime_words(int mode, size_t n);
 int cck_sigma_prime(int mode, size_t n, size_t rstride, const uint8_t* d_s1, const uint8_t* d_s2, const uint8_t* d_rnd,
                     uint32_t* d_scratch, uint8_t* d_o1, uint8_t* d_o2, hipStream_t st);
@@ -329,8 +334,8 @@ struct cc_ctx {
     std::vector<ncclComm_t> comms;
     DevBuf rlc_gath;  // per peer: gathered partials (ndev x RLC_PART_WORDS words)
     // concurrent verify batches (cc_set_concurrency): with K > 1 slots, cc_verify_batch_device /
-    // cc_verify_batch_pervk_device / cc_pok_verify_batch_device / cc_rlc_partial_device /
-    // cc_pok_rlc_partial_device calls take the
+    // cc_verify_batch_pervk_device / cc_pok_verify_batch_device / cc_pok_verify_batch_pervk_device /
+    // cc_rlc_partial_device / cc_pok_rlc_partial_device calls take the
     // slots round-robin and are ordered only after the context's earlier work (tables, params) and the
     // same slot's previous batch, so K batches on K caller streams overlap (slots.h).  pool.recs[0] is
     // the context's own workspaces (prep / flags / fbuf / vkb / scratch / pok_idx / wide_*); vslots
@@ -2043,6 +2048,127 @@ cc_status cc_pok_verify_batch_rlc(cc_ctx* c, size_t n, size_t q, size_t r, size_
                                   const uint8_t* chal, const uint64_t* rev_idx, const uint8_t* rev_msgs,
                                   uint8_t* verdicts) {
     return pok_host(c, n, q, r, nresp, s1, s2, J, T, resp, chal, rev_idx, rev_msgs, verdicts, nullptr, 1);
+}
+
+// ---------------------------------------------------------------- PoK verify, one verkey per proof
+// (pok_pervk.hip): the prep's Straus tables live in w.vkb, the rest is launch_pok's
+static cc_status launch_pok_pervk(cc_ctx* c, const VerifyWork& w, size_t n, size_t q, size_t r, const uint8_t* d_s1,
+                                  const uint8_t* d_s2, const uint8_t* d_J, const uint8_t* d_T, const uint8_t* d_resp,
+                                  const uint8_t* d_chal, const uint32_t* d_idx, const uint8_t* d_rev_msgs,
+                                  const uint8_t* d_vkX, const uint8_t* d_vkY, uint8_t* d_verdicts, uint8_t* d_gt,
+                                  hipStream_t st) {
+    if (c->timing) (void)hipEventRecord(c->ev[0], st);
+    KCK(cck_prep_pok_var(c->mode, n, (int)q, (int)r, d_s1, d_s2, d_J, d_T, d_resp, d_chal, d_rev_msgs, d_idx, d_vkX,
+                         d_vkY, c->gtilde_aff.as<uint32_t>(), c->gtilde_inf, w.vkb->as<uint32_t>(),
+                         w.prep->as<uint32_t>(), w.flags->as<uint32_t>(), st));
+    if (c->timing) (void)hipEventRecord(c->ev[1], st);
+    cc_status ms = launch_miller(c, w, n, st);
+    if (ms) return ms;
+    if (c->timing) (void)hipEventRecord(c->ev[2], st);
+    KCK(cck_fexp(n, w.fbuf->as<uint32_t>(), w.scratch->as<uint32_t>(), w.flags->as<uint32_t>(), d_verdicts, d_gt,
+                 kFexpWideMax, st));
+    if (c->timing) (void)hipEventRecord(c->ev[3], st);
+    return CC_OK;
+}
+
+// the checks of cc_pok_verify_batch_device in its order, without a loaded verkey (q <= the pervk ceiling)
+static cc_status pok_pervk_check(const cc_ctx* c, size_t n, size_t q, size_t r, size_t nresp, const void* s1,
+                                 const void* s2, const void* J, const void* T, const void* resp, const void* chal,
+                                 const uint64_t* rev_idx, const void* rev_msgs, const void* vkX, const void* vkY,
+                                 const void* verdicts, std::vector<uint32_t>& idx) {
+    if (!c || (n && (!s1 || !s2 || !J || !T || !chal || !verdicts || !vkX || (q && !vkY) || (nresp && !resp) ||
+                     (r && (!rev_idx || !rev_msgs)))))
+        return CC_ERR_DECODE;
+    if (!c->have_params) return CC_ERR_STATE;
+    if (q > 4096) return CC_ERR_DECODE;
+    if (r && !rev_idx) return CC_ERR_DECODE;  // n = 0 with a revealed set still needs its indices
+    cc_status s = check_revealed(q, r, rev_idx, idx);
+    if (s) return s;
+    if (nresp != q - r + 1) return CC_ERR_BASES_EXPS;
+    if (n > kMaxBatch) return CC_ERR_DECODE;
+    return CC_OK;
+}
+
+cc_status cc_pok_verify_batch_pervk_device(cc_ctx* c, size_t n, size_t q, size_t r, size_t nresp,
+                                           const uint8_t* d_s1, const uint8_t* d_s2, const uint8_t* d_J,
+                                           const uint8_t* d_T, const uint8_t* d_resp, const uint8_t* d_chal,
+                                           const uint64_t* rev_idx, const uint8_t* d_rev_msgs, const uint8_t* d_vkX,
+                                           const uint8_t* d_vkY, uint8_t* d_verdicts, uint8_t* d_gt, void* stream) {
+    c = primary(c);  // a device set forwards to its first device
+    std::vector<uint32_t> idx;
+    cc_status s = pok_pervk_check(c, n, q, r, nresp, d_s1, d_s2, d_J, d_T, d_resp, d_chal, rev_idx, d_rev_msgs, d_vkX,
+                                  d_vkY, d_verdicts, idx);
+    if (s) return s;
+    if (!n) return CC_OK;
+    HIPCK(hipSetDevice(c->device));
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    const size_t vkw = cck_prep_pok_var_words(c->mode, n, q) * 4;
+    if (c->concurrency > 1) {  // the next concurrency slot (cc_set_concurrency): its own tables and indices
+        int k = 0;
+        VerifyWork w;
+        s = slot_begin(c, st, cc::slots::verify_sizes(n, vkw, 0, idx.size() * 4 + 4), k, w);
+        if (s) return s;
+        SlotFence fence(c->pool, c->dev, k, st);
+        if (r) KCK(c->stage[(size_t)k].upload(w.idx->p, idx.data(), idx.size() * 4, st));  // pinned ring
+        s = launch_pok_pervk(c, w, n, q, r, d_s1, d_s2, d_J, d_T, d_resp, d_chal, w.idx->as<uint32_t>(), d_rev_msgs,
+                             d_vkX, d_vkY, d_verdicts, d_gt, st);
+        if (s) return s;
+        return fence.close() ? CC_ERR_HIP : CC_OK;
+    }
+    s = ensure_work(c, n);
+    if (s) return s;
+    if (c->vkb.bytes < vkw) drain_slots(c);  // slot 0's batch may still read it
+    StreamOrder order(c, st);
+    if (c->vkb.ensure(vkw) || c->pok_idx.ensure(idx.size() * 4)) return CC_ERR_HIP;
+    HIPCK(hipMemcpyAsync(c->pok_idx.p, idx.data(), idx.size() * 4, hipMemcpyHostToDevice, st));
+    s = launch_pok_pervk(c, ctx_work(c), n, q, r, d_s1, d_s2, d_J, d_T, d_resp, d_chal, c->pok_idx.as<uint32_t>(),
+                         d_rev_msgs, d_vkX, d_vkY, d_verdicts, d_gt, st);
+    if (s) return s;
+    if (c->timing) collect_timing(c);
+    return CC_OK;
+}
+
+// the host form: one upload, the device form on the context's stream, one download
+cc_status cc_pok_verify_batch_pervk(cc_ctx* c, size_t n, size_t q, size_t r, size_t nresp, const uint8_t* s1,
+                                    const uint8_t* s2, const uint8_t* J, const uint8_t* T, const uint8_t* resp,
+                                    const uint8_t* chal, const uint64_t* rev_idx, const uint8_t* rev_msgs,
+                                    const uint8_t* vkX, const uint8_t* vkY, uint8_t* verdicts, uint8_t* gt) {
+    c = primary(c);  // a device set forwards to its first device
+    std::vector<uint32_t> idx;
+    cc_status s = pok_pervk_check(c, n, q, r, nresp, s1, s2, J, T, resp, chal, rev_idx, rev_msgs, vkX, vkY, verdicts, idx);
+    if (s) return s;
+    if (!n) return CC_OK;
+    HIPCK(hipSetDevice(c->device));
+    drain_slots(c);  // concurrent device batches may still read the staging buffers
+    const size_t sb = (size_t)sig_bytes(c->mode), ob = (size_t)oth_bytes(c->mode);
+    hipStream_t st = c->stream;
+    DevBuf& dJ = c->in_aux[0];
+    DevBuf& dT = c->in_aux[1];
+    DevBuf& dR = c->in_aux[2];
+    DevBuf& dC = c->in_aux[3];
+    DevBuf& dM = c->in_aux[4];
+    if (c->in_s1.ensure(n * sb) || c->in_s2.ensure(n * sb) || dJ.ensure(n * ob) || dT.ensure(n * ob) ||
+        dR.ensure(n * nresp * 48 + 16) || dC.ensure(n * 48) || dM.ensure(n * r * 48 + 16) || c->in_vkX.ensure(n * ob) ||
+        c->in_vkY.ensure(n * q * ob + 16) || c->verdicts.ensure(n) || (gt && c->gt.ensure(n * 576)))
+        return CC_ERR_HIP;
+    HIPCK(hipMemcpyAsync(c->in_s1.p, s1, n * sb, hipMemcpyHostToDevice, st));
+    HIPCK(hipMemcpyAsync(c->in_s2.p, s2, n * sb, hipMemcpyHostToDevice, st));
+    HIPCK(hipMemcpyAsync(dJ.p, J, n * ob, hipMemcpyHostToDevice, st));
+    HIPCK(hipMemcpyAsync(dT.p, T, n * ob, hipMemcpyHostToDevice, st));
+    HIPCK(hipMemcpyAsync(dR.p, resp, n * nresp * 48, hipMemcpyHostToDevice, st));
+    HIPCK(hipMemcpyAsync(dC.p, chal, n * 48, hipMemcpyHostToDevice, st));
+    if (r) HIPCK(hipMemcpyAsync(dM.p, rev_msgs, n * r * 48, hipMemcpyHostToDevice, st));
+    HIPCK(hipMemcpyAsync(c->in_vkX.p, vkX, n * ob, hipMemcpyHostToDevice, st));
+    if (q) HIPCK(hipMemcpyAsync(c->in_vkY.p, vkY, n * q * ob, hipMemcpyHostToDevice, st));
+    s = cc_pok_verify_batch_pervk_device(c, n, q, r, nresp, c->in_s1.as<uint8_t>(), c->in_s2.as<uint8_t>(),
+                                         dJ.as<uint8_t>(), dT.as<uint8_t>(), dR.as<uint8_t>(), dC.as<uint8_t>(), rev_idx,
+                                         dM.as<uint8_t>(), c->in_vkX.as<uint8_t>(), c->in_vkY.as<uint8_t>(),
+                                         c->verdicts.as<uint8_t>(), gt ? c->gt.as<uint8_t>() : nullptr, st);
+    if (s) return s;
+    HIPCK(hipMemcpyAsync(verdicts, c->verdicts.p, n, hipMemcpyDeviceToHost, st));
+    if (gt) HIPCK(hipMemcpyAsync(gt, c->gt.p, n * 576, hipMemcpyDeviceToHost, st));
+    HIPCK(hipStreamSynchronize(st));
+    return CC_OK;
 }
 
 

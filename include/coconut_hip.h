@@ -11,7 +11,7 @@
  *        replaces  Signature::aggregate           src/signature.rs:448-470
  *   cc_verkey_aggregate_batch
  *        replaces  Verkey::aggregate              src/signature.rs:483-526
- *   cc_pok_verify_batch
+ *   cc_pok_verify_batch / cc_pok_verify_batch_pervk(_device)
  *        replaces  ps_sig PoKOfSignatureProof::verify [EXT], called at src/pok_sig.rs:103-105
  *   cc_pok_init_batch / cc_pok_gen_proof_batch
  *        replaces  ps_sig PoKOfSignature::init / gen_proof [EXT], called at src/pok_sig.rs:80-100
@@ -142,8 +142,8 @@ cc_status cc_verify_batch_pervk_device(cc_ctx* ctx, size_t n, size_t q, const ui
                                        void* stream);
 
 /* Concurrent verify batches on one context: with `slots` = K > 1, cc_verify_batch_device,
- * cc_verify_batch_pervk_device, cc_pok_verify_batch_device, cc_rlc_partial_device and
- * cc_pok_rlc_partial_device calls take K
+ * cc_verify_batch_pervk_device, cc_pok_verify_batch_device, cc_pok_verify_batch_pervk_device,
+ * cc_rlc_partial_device and cc_pok_rlc_partial_device calls take K
  * workspace slots round-robin (each slot its own prep SoA, flags, Miller values, PoK d J tables and RLC
  * delta/fold buffers; the verkey tables are shared)
  * and are ordered only after the context's earlier work (tables, params) and the same slot's previous
@@ -256,6 +256,40 @@ cc_status cc_pok_verify_batch_device(cc_ctx* ctx, size_t n, size_t q, size_t r, 
                                      const uint8_t* d_responses, const uint8_t* d_chal, const uint64_t* revealed_idx,
                                      const uint8_t* d_revealed_msgs, uint8_t* d_verdicts, uint8_t* d_gt_or_null,
                                      void* stream);
+
+/* PoKOfSignatureProof::verify(&vk_i, &params, revealed_msgs, &chal) for each proof i with ITS OWN verkey
+ * (src/pok_sig.rs:103-105 takes the verkey per call): a verifier whose credentials come from different
+ * authority subsets holds one aggregated verkey per credential (what cc_verkey_aggregate_ids_device and
+ * cc_aggregate_credential_batch_device write).
+ *   d_vk_X : n x OtherGroup        d_vk_Y : n x q x OtherGroup   (cc_verify_batch_pervk_device's layout)
+ * Every other argument has the meaning, order and encoding it has in cc_pok_verify_batch_device:
+ * revealed_idx is a host array shared by the batch (any order, unique, < q), responses are ordered
+ * [g~, Y~_i for hidden i ascending], revealed messages are in revealed_idx order.  Per proof:
+ *   resp_0 g~ + sum_hidden resp_j Y~_i,j + chal J - T == O   and   e(sigma'_1, X~_i + J +
+ *   sum_revealed m_z Y~_i,idx[z]) e(-sigma'_2, g~) == 1,
+ * with the reference's handling of every input: a point that does not decode is the identity, scalars
+ * are reduced mod r, bases and J need not lie in the order-r subgroup.
+ * Needs cc_set_params only: no cc_set_verkey, and q is not compared with a loaded verkey.
+ * Checks, in order and before the n = 0 shortcut: NULL context, or a NULL buffer with n > 0 (d_vk_X, and
+ * d_vk_Y when q > 0, among them) -> CC_ERR_DECODE; no params -> CC_ERR_STATE; q > 4096 -> CC_ERR_DECODE;
+ * a revealed index >= q -> CC_ERR_LEN, a repeated one -> CC_ERR_DECODE; nresp != q - r + 1 ->
+ * CC_ERR_BASES_EXPS; n > CC_MAX_BATCH -> CC_ERR_DECODE.  n = 0 is then a no-op (buffers may be NULL).
+ * Asynchronous on `stream` (NULL: the context stream); takes a concurrency slot (cc_set_concurrency)
+ * as the two calls it combines do.  Device memory: the prep's per-proof window tables, 8 (q + 2) points
+ * a proof — at q = 32, 67,584 B a proof in CC_SIG_G2 and 132,864 B in CC_SIG_G1 (4.43 GB and 8.71 GB at
+ * 65,536 proofs), held by the context (per slot) until it is destroyed.
+ * cc_pok_verify_batch_pervk: the same with host pointers: one upload, the device form, one download. */
+cc_status cc_pok_verify_batch_pervk_device(cc_ctx* ctx, size_t n, size_t q, size_t r, size_t nresp,
+                                           const uint8_t* d_sigma1, const uint8_t* d_sigma2, const uint8_t* d_J,
+                                           const uint8_t* d_T, const uint8_t* d_responses, const uint8_t* d_chal,
+                                           const uint64_t* revealed_idx, const uint8_t* d_revealed_msgs,
+                                           const uint8_t* d_vk_X, const uint8_t* d_vk_Y, uint8_t* d_verdicts,
+                                           uint8_t* d_gt_or_null, void* stream);
+cc_status cc_pok_verify_batch_pervk(cc_ctx* ctx, size_t n, size_t q, size_t r, size_t nresp, const uint8_t* sigma1,
+                                    const uint8_t* sigma2, const uint8_t* J, const uint8_t* T,
+                                    const uint8_t* responses, const uint8_t* chal, const uint64_t* revealed_idx,
+                                    const uint8_t* revealed_msgs, const uint8_t* vk_X, const uint8_t* vk_Y,
+                                    uint8_t* verdicts, uint8_t* gt_or_null);
 
 /* Holder side: ps_sig PoKOfSignature::init / gen_proof [EXT] (reference src/pok_sig.rs:80-100) and
  * BlindSignature::unblind (src/signature.rs:436-443), what cc_pok_verify_batch consumes.

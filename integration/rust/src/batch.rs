@@ -192,6 +192,44 @@ pub fn pok_verify_batch(proofs: &[(Vec<u8>, Vec<u8>, Vec<u8>, Vec<u8>, Vec<Field
     v.into_iter().map(|b| b == 1).collect()
 }
 
+/// PoKOfSignatureProof::verify for n proofs, proof i against ITS OWN verkey `vks[i]` (a verifier whose
+/// credentials come from different authority subsets holds one aggregated verkey per credential).  The
+/// other arguments as `pok_verify_batch`; revealed indices may be in any order.  Binds params only.
+pub fn pok_verify_batch_pervk(proofs: &[(Vec<u8>, Vec<u8>, Vec<u8>, Vec<u8>, Vec<FieldElement>)],
+                              chal: &[FieldElement], revealed_idx: &[u64], revealed_msgs: &[Vec<FieldElement>],
+                              vks: &[Verkey], params: &Params, ctx: &HipCtx) -> Vec<bool> {
+    let (n, r) = (proofs.len(), revealed_idx.len());
+    if n == 0 { return Vec::new(); }
+    assert_eq!(vks.len(), n, "one verkey per proof");  // len-guard
+    let q = vks[0].Y_tilde.len();
+    let nresp = proofs[0].4.len();
+    let (sb, ob) = (ctx.sig_bytes(), ctx.oth_bytes());
+    assert!(vks.iter().all(|v| v.Y_tilde.len() == q), "the same message count for every verkey");  // len-guard
+    assert_eq!(chal.len(), n, "one challenge per proof");  // len-guard
+    assert!(revealed_msgs.len() == n && revealed_msgs.iter().all(|m| m.len() == r),
+            "r revealed messages per proof");  // len-guard
+    assert!(proofs.iter().all(|p| p.4.len() == nresp), "the same response count for every proof");  // len-guard
+    assert!(proofs.iter().all(|p| p.0.len() == sb && p.1.len() == sb && p.2.len() == ob && p.3.len() == ob),
+            "proof part encodings (sigma'_1, sigma'_2: SignatureGroup; J, T: OtherGroup)");  // len-guard
+    ctx.set_params(&params.g_tilde.to_bytes());
+    let cat = |f: &dyn Fn(&(Vec<u8>, Vec<u8>, Vec<u8>, Vec<u8>, Vec<FieldElement>)) -> Vec<u8>| -> Vec<u8> {
+        proofs.iter().flat_map(|p| f(p)).collect()
+    };
+    let (s1, s2, j, t) = (cat(&|p| p.0.clone()), cat(&|p| p.1.clone()), cat(&|p| p.2.clone()), cat(&|p| p.3.clone()));
+    let resp = cat(&|p| p.4.iter().flat_map(|v| v.to_bytes()).collect());
+    let ch: Vec<u8> = chal.iter().flat_map(|c| c.to_bytes()).collect();
+    let rm: Vec<u8> = revealed_msgs.iter().flatten().flat_map(|m| m.to_bytes()).collect();
+    let vx: Vec<u8> = vks.iter().flat_map(|v| v.X_tilde.to_bytes()).collect();
+    let vy: Vec<u8> = vks.iter().flat_map(|v| v.Y_tilde.iter().flat_map(|y| y.to_bytes())).collect();
+    assert!(vx.len() == n * ob && vy.len() == n * q * ob, "verkey encodings (OtherGroup)");  // len-guard
+    let mut v = vec![0u8; n];
+    ctx.check(unsafe { cc_pok_verify_batch_pervk(ctx.raw, n, q, r, nresp, s1.as_ptr(), s2.as_ptr(), j.as_ptr(),
+                                                 t.as_ptr(), resp.as_ptr(), ch.as_ptr(), revealed_idx.as_ptr(),
+                                                 rm.as_ptr(), vx.as_ptr(), vy.as_ptr(), v.as_mut_ptr(),
+                                                 std::ptr::null_mut()) });
+    v.into_iter().map(|b| b == 1).collect()
+}
+
 /// One holder-side proof as its serialized parts: (sigma'_1, sigma'_2, J, T, responses), the tuple
 /// `pok_verify_batch` takes.
 pub type ProofParts = (Vec<u8>, Vec<u8>, Vec<u8>, Vec<u8>, Vec<FieldElement>);

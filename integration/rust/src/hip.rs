@@ -76,6 +76,18 @@ extern "C" {
                                       d_responses: *const u8, d_chal: *const u8, revealed_idx: *const u64,
                                       d_revealed_msgs: *const u8, d_verdicts: *mut u8, d_gt: *mut u8,
                                       stream: *mut c_void) -> c_int;
+    // the same with one verkey per proof (d_vk_x: n x OtherGroup, d_vk_y: n x q x OtherGroup); needs params only
+    pub fn cc_pok_verify_batch_pervk_device(ctx: *mut CcCtx, n: usize, q: usize, r: usize, nresp: usize,
+                                            d_sigma1: *const u8, d_sigma2: *const u8, d_j: *const u8,
+                                            d_t: *const u8, d_responses: *const u8, d_chal: *const u8,
+                                            revealed_idx: *const u64, d_revealed_msgs: *const u8,
+                                            d_vk_x: *const u8, d_vk_y: *const u8, d_verdicts: *mut u8,
+                                            d_gt: *mut u8, stream: *mut c_void) -> c_int;
+    pub fn cc_pok_verify_batch_pervk(ctx: *mut CcCtx, n: usize, q: usize, r: usize, nresp: usize,
+                                     sigma1: *const u8, sigma2: *const u8, j: *const u8, t: *const u8,
+                                     responses: *const u8, chal: *const u8, revealed_idx: *const u64,
+                                     revealed_msgs: *const u8, vk_x: *const u8, vk_y: *const u8,
+                                     verdicts: *mut u8, gt: *mut u8) -> c_int;
     // holder side: PoKOfSignature::init / gen_proof (pok_sig.rs:80-100), BlindSignature::unblind (signature.rs:436-443)
     pub fn cc_pok_init_batch(ctx: *mut CcCtx, n: usize, q: usize, r: usize, nresp: usize, sigma1: *const u8,
                              sigma2: *const u8, msgs: *const u8, revealed_idx: *const u64, rand: *const u8,
