@@ -3,7 +3,8 @@
 Mirrors 3for/coconut-rust (`/root/reference/src/lib.rs:26-31` module list) for the hot path only:
 `signature` (Signature::verify / aggregate, Verkey::aggregate + batch entry points), `pok_sig`
 (PoKOfSignature::init / gen_proof, PoKOfSignatureProof::verify), `issuance` (issuer-side batches, the
-holder's SignatureRequest::new, SignatureRequestPoK and BlindSignature::unblind), `errors`.  Every computation runs in libcoconut_hip.so on the GPU; importing
+holder's SignatureRequest::new, SignatureRequestPoK and BlindSignature::unblind), `keygen`
+(trusted_party_SSS_keygen / trusted_party_PVSS_keygen and the decentralized keygen's combine), `errors`.  Every computation runs in libcoconut_hip.so on the GPU; importing
 this package on a machine without the built library raises immediately.
 """
 from .errors import CoconutError, CoconutErrorKind  # noqa: F401
@@ -18,3 +19,6 @@ from .issuance import (blind_sign_batch, sigreq_verify_batch, vss_verify_batch, 
                        SignatureRequest, SignatureRequestPoK, sigreq_new_batch, sigreq_pok_init_batch,
                        sigreq_pok_gen_proof_batch, sigreq_pok_to_bytes_batch, sigreq_challenge_batch,
                        sigreq_proof_bytes, sigreq_verify_batch_device, blind_sign_batch_device)
+from .keygen import (Signer, Sigkey, keygen_deal_batch, keygen_combine_batch,  # noqa: F401
+                     keygen_deal_batch_device, keygen_combine_batch_device,
+                     trusted_party_SSS_keygen, trusted_party_PVSS_keygen)

@@ -85,6 +85,14 @@ _SIGS = {
     "cc_sigreq_pok_gen_proof_batch_device": (c_int, [c_p, c_sz, c_sz, c_sz, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
     "cc_sigreq_verify_batch_device": (c_int, [c_p, c_sz, c_sz, c_sz, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
     "cc_blind_sign_batch_device": (c_int, [c_p, c_sz, c_sz, c_sz, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "cc_set_keygen_params": (c_int, [c_p, c_p, c_p, c_p, c_int]),
+    "cc_keygen_deal_batch": (c_int, [c_p, c_sz, c_sz, c_sz, c_sz, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "cc_keygen_deal_batch_device": (c_int, [c_p, c_sz, c_sz, c_sz, c_sz, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
+                                            c_p]),
+    "cc_keygen_combine_batch": (c_int, [c_p, c_sz, c_sz, c_sz, c_sz, c_sz, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
+                                        c_p, c_p, c_p]),
+    "cc_keygen_combine_batch_device": (c_int, [c_p, c_sz, c_sz, c_sz, c_sz, c_sz, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
+                                               c_p, c_p, c_p, c_p, c_p, c_p]),
     "cc_vss_verify_batch": (c_int, [c_p, c_sz, c_sz, c_p, c_p, c_p, c_sz, c_p, c_p, c_p, c_p]),
     "cc_fixed_base_mul": (c_int, [c_p, c_int, c_p, c_sz, c_p, c_p]),
     "cc_rlc_partial_words": (c_int, []),

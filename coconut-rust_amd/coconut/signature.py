@@ -220,6 +220,26 @@ class Context:
         check(lib.cc_set_request_params(self.h, q, pg, ph, int(table_bits)), "cc_set_request_params")
         self._rq = key
 
+    def set_keygen_params(self, g_tilde: bytes, g: bytes = None, h: bytes = None, table_bits: int = 0):
+        """Params.g_tilde and the Pedersen generators g, h (G1; both None for Shamir only) for the keygen
+        entry points (cc_set_keygen_params): builds the fixed-base tables keygen_deal_batch /
+        keygen_combine_batch read.  table_bits as set_request_params; the same bases again keep their tables."""
+        need(g_tilde, self.mode.other_bytes, "g_tilde")
+        if (g is None) != (h is None):
+            raise CoconutError(-4, "g and h: both or neither")
+        if g is not None:
+            need(g, G1_BYTES, "g")
+            need(h, G1_BYTES, "h")
+        key = (bytes(g_tilde), None if g is None else bytes(g), None if h is None else bytes(h), int(table_bits))
+        kg = getattr(self, "_kg", None)
+        if kg is not None and kg[:3] == key[:3] and table_bits in (0, kg[3]):
+            return
+        keep = [buf(g_tilde), buf(g), buf(h)]
+        self._kg = None  # a failed call leaves the context without keygen params
+        check(lib.cc_set_keygen_params(self.h, keep[0][0], keep[1][0], keep[2][0], int(table_bits)),
+              "cc_set_keygen_params")
+        self._kg = key
+
     def set_concurrency(self, slots: int):
         """cc_set_concurrency: K verify batches in flight on K caller streams (workspace slots taken
         round-robin by the *_device verify calls; 1 = every call ordered against every other)."""

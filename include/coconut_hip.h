@@ -20,6 +20,9 @@
  *   cc_sigreq_new_batch / cc_sigreq_pok_init_batch / cc_sigreq_pok_gen_proof_batch
  *        replaces  SignatureRequest::new, SignatureRequestPoK::init / gen_proof
  *                                                 src/signature.rs:124-192, 216-320
+ *   cc_keygen_deal_batch / cc_keygen_combine_batch
+ *        replaces  trusted_party_SSS_keygen, trusted_party_PVSS_keygen, keygen_from_shares and the
+ *                  decentralized keygen's final sums  src/keygen.rs:17-122, 124-205
  *   cc_set_params / cc_set_verkey
  *        the Params (src/signature.rs:13-17, only g_tilde is read by verify) and Verkey
  *        (src/signature.rs:46-49) a batch is checked against
@@ -513,6 +516,78 @@ cc_status cc_blind_sign_batch_device(cc_ctx* ctx, size_t n, size_t q, size_t k, 
 cc_status cc_vss_verify_batch(cc_ctx* ctx, size_t n, size_t t, const uint8_t* g, const uint8_t* h,
                               const uint8_t* commitments, size_t n_sets, const uint32_t* set_of, const uint64_t* ids,
                               const uint8_t* shares, uint8_t* verdicts);
+
+/* Keygen, the dealer's side (reference src/keygen.rs): m independent trusted-party keygens in one call, and
+ * the last step of the decentralized keygen.  OG = an OtherGroup encoding.
+ *
+ * cc_set_keygen_params binds Params.g_tilde (one OG) and the Pedersen generators g, h (G1, 97 B each, as
+ * keygen.rs:78-79) and builds the context's own fixed-base window tables: one OtherGroup base for g~ and a
+ * two-base G1 table [g, h].  vss_g and vss_h may both be NULL (Shamir only); exactly one NULL, NULL ctx or
+ * g_tilde, or table_bits outside {0, 8..16}: CC_ERR_DECODE.  table_bits in 8..16 forces the window width (a
+ * width that does not fit the free HBM: CC_ERR_HIP); 0 takes the widest of {16, 13, 12, 10, 8} whose tables
+ * fit min(4 GiB, half the free HBM), 8 bits if the allocation fails.  The verkey, issuer and request tables
+ * and cc_set_table_bits are untouched.  An identity or undecodable base is skipped in every sum, so its
+ * multiples are the identity encoding.  A failed call leaves the context without keygen params.
+ *
+ * cc_keygen_deal_batch: trusted_party_SSS_keygen (keygen.rs:53-71) or trusted_party_PVSS_keygen (74-122)
+ * with keygen_from_shares (17-45), m times; the caller supplies the randomness, the polynomials.
+ *   coeffs   m x (q + 1) x t x 48 : polynomial 0 of a keygen shares x, polynomial 1 + j shares y_j;
+ *            coefficient i is that of degree i, coefficient 0 the secret
+ *   coeffs_t the same layout, the blinding polynomials f' of PedersenVSS::deal; NULL selects Shamir:
+ *            out_xt, out_yt and out_comm are then not written and may be NULL
+ *   signer ids are 1 .. total, as in the reference
+ *   -> out_x  m x total x 48      f_0(id)           out_y  m x total x q x 48   f_{1+j}(id)
+ *      out_xt, out_yt             the same shapes, from f'
+ *      out_comm m x (q + 1) x t x 97   C_i = f_i g + f'_i h
+ *      out_X  m x total x OG      g~ * x_id         out_Y  m x total x q x OG   g~ * y_id,j
+ *   The outputs chain without repacking: out_comm is cc_vss_verify_batch's `commitments` with n_sets =
+ *   m (q + 1); a keygen's out_X / out_Y slice is cc_set_issuers' X / Y; a signer's x | y is what
+ *   cc_blind_sign_batch takes.
+ *
+ * cc_keygen_combine_batch: the last step of the decentralized keygen (keygen.rs:124-205,
+ * PedersenDVSSParticipant::compute_final_comm_coeffs_and_shares [EXT, recalled]).  The inputs are the outputs
+ * of a deal with m x d keygens, read as m groups of d dealers; every output is the sum over the dealer axis:
+ * shares and blinding shares mod r, commitments as G1 point sums (equal addends double, opposite ones give
+ * the identity, an identity or undecodable addend is skipped); out_X / out_Y are g~ times the combined
+ * shares.  xt, yt, comm and their outputs may all be NULL; one of them given makes all of them required.
+ * [EXT, recalled]: the secret_sharing crate is not on this machine.  The contract is the one
+ * setup_signers_for_test (keygen.rs:169-205) relies on: a participant's final share is the sum of every
+ * dealer's share for its id, the distributed secret is the sum of the dealers' secrets, and the final
+ * coefficient commitments are the dealers' sums.
+ *
+ * Checks, in this order and before the m = 0 shortcut: NULL context: CC_ERR_DECODE; a NULL buffer the call
+ * would read or write with m > 0 (q = 0 is allowed, the y buffers may then be NULL): CC_ERR_DECODE; no
+ * keygen params, or coeffs_t / comm given while no g, h are bound: CC_ERR_STATE; t = 0 or t > total:
+ * CC_ERR_THRESHOLD (our choice: the crate that would decide is not on this machine); total > CC_MAX_IDS,
+ * q > CC_MAX_Q, m total (q + 1) or m (q + 1) t above CC_MAX_BATCH (combine: with m d for m), or d = 0:
+ * CC_ERR_DECODE; m = 0: CC_OK, nothing launched.
+ * Scalars are reduced mod r, outputs are canonical, a zero share gives the identity encoding; nothing is
+ * rejected that the reference would not reject.
+ * The *_device forms take device pointers, are asynchronous on `stream` (NULL: the context stream) and
+ * take no concurrency slot: they first wait for the slots' batches.  A device set forwards to its first
+ * device.
+ * Secrets: the host forms copy the coefficients (combine: the dealers' shares) to the device and write the
+ * shares there; they overwrite those device copies with zeros before returning (the kernels keep the window
+ * digits in registers, there is no digit scratch).  The *_device forms read the caller's buffers in place;
+ * they have no scratch of their own. */
+cc_status cc_set_keygen_params(cc_ctx* ctx, const uint8_t* g_tilde, const uint8_t* vss_g, const uint8_t* vss_h,
+                               int table_bits);
+cc_status cc_keygen_deal_batch(cc_ctx* ctx, size_t m, size_t q, size_t t, size_t total, const uint8_t* coeffs,
+                               const uint8_t* coeffs_t, uint8_t* out_x, uint8_t* out_y, uint8_t* out_xt,
+                               uint8_t* out_yt, uint8_t* out_comm, uint8_t* out_X, uint8_t* out_Y);
+cc_status cc_keygen_deal_batch_device(cc_ctx* ctx, size_t m, size_t q, size_t t, size_t total,
+                                      const uint8_t* d_coeffs, const uint8_t* d_coeffs_t, uint8_t* d_out_x,
+                                      uint8_t* d_out_y, uint8_t* d_out_xt, uint8_t* d_out_yt, uint8_t* d_out_comm,
+                                      uint8_t* d_out_X, uint8_t* d_out_Y, void* stream);
+cc_status cc_keygen_combine_batch(cc_ctx* ctx, size_t m, size_t d, size_t q, size_t t, size_t total,
+                                  const uint8_t* x, const uint8_t* y, const uint8_t* xt, const uint8_t* yt,
+                                  const uint8_t* comm, uint8_t* out_x, uint8_t* out_y, uint8_t* out_xt,
+                                  uint8_t* out_yt, uint8_t* out_comm, uint8_t* out_X, uint8_t* out_Y);
+cc_status cc_keygen_combine_batch_device(cc_ctx* ctx, size_t m, size_t d, size_t q, size_t t, size_t total,
+                                         const uint8_t* d_x, const uint8_t* d_y, const uint8_t* d_xt,
+                                         const uint8_t* d_yt, const uint8_t* d_comm, uint8_t* d_out_x,
+                                         uint8_t* d_out_y, uint8_t* d_out_xt, uint8_t* d_out_yt,
+                                         uint8_t* d_out_comm, uint8_t* d_out_X, uint8_t* d_out_Y, void* stream);
 
 /* Batch fixed-base scalar multiplication out_i = k_i * base (group 1 = G1, 2 = G2); scalars n x 48 B
  * big-endian Fr, out n encodings.  The keygen derivation g~ * x_i (reference src/keygen.rs:27-32)

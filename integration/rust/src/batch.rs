@@ -5,6 +5,7 @@
 // (`len-guard` lines; tests/test_rust_binding.py checks they are present): the C ABI reads n * q * 48
 // bytes of messages, n * len entries of a batch, ..., so a shorter Vec would be a heap over-read.
 use crate::hip::*;
+use crate::keygen::Signer;
 use crate::signature::{BlindSignature, Params, Signature, SignatureRequest, Sigkey, Verkey};
 use crate::{OtherGroup, SignatureGroup};
 use amcl_wrapper::field_elem::FieldElement;
@@ -365,6 +366,66 @@ pub fn sigreq_prove_batch(messages: &[Vec<FieldElement>], k: usize, elgamal_pks:
         let rs = (0..k + 1).map(|j| FieldElement::from_bytes(&rand[(i * (k + 1) + j) * 48..(i * (k + 1) + j + 1) * 48])
                                 .unwrap()).collect();
         (req, rs, proofs[i * pb..(i + 1) * pb].to_vec(), c)
+    }).collect()
+}
+
+/// One dealt keygen: (secret_x, secret_y, signers) as trusted_party_SSS_keygen returns them, and with
+/// Pedersen generators the coefficient commitments ((q + 1) x threshold, polynomial-major) and every
+/// signer's blinding shares (x_t | y_t[q], signer-major) of trusted_party_PVSS_keygen.
+pub type DealtKeygen = (FieldElement, Vec<FieldElement>, Vec<Signer>, Option<(Vec<G1>, Vec<FieldElement>)>);
+
+/// trusted_party_SSS_keygen (keygen.rs:53-71; `vss` None) or trusted_party_PVSS_keygen (74-122; `vss` the
+/// Pedersen generators g, h) for m independent committees of `total` signers with threshold `threshold`:
+/// fresh polynomials per keygen (FieldElement::random), every share, commitment and verkey on the GPU.
+pub fn keygen_deal_batch(m: usize, threshold: usize, total: usize, params: &Params, vss: Option<(&G1, &G1)>,
+                         ctx: &HipCtx) -> Vec<DealtKeygen> {
+    if m == 0 { return Vec::new(); }
+    let (q, t, ob) = (params.h.len(), threshold, ctx.oth_bytes());
+    assert!(t > 0 && t <= total, "threshold of total signers");  // len-guard
+    let gt = params.g_tilde.to_bytes();
+    let gh = vss.map(|(g, h)| (g.to_bytes(), h.to_bytes()));
+    assert_eq!(gt.len(), ob, "g_tilde encoding");  // len-guard
+    assert!(gh.iter().all(|(g, h)| g.len() == 97 && h.len() == 97), "Pedersen generator encodings");  // len-guard
+    let null = std::ptr::null::<u8>();
+    ctx.check(unsafe { cc_set_keygen_params(ctx.raw, gt.as_ptr(), gh.as_ref().map_or(null, |p| p.0.as_ptr()),
+                                            gh.as_ref().map_or(null, |p| p.1.as_ptr()), 0) });
+    let nc = m * (q + 1) * t;
+    let cf: Vec<u8> = (0..nc).flat_map(|_| FieldElement::random().to_bytes()).collect();
+    let ct: Vec<u8> = if vss.is_some() { (0..nc).flat_map(|_| FieldElement::random().to_bytes()).collect() }
+                      else { Vec::new() };
+    assert!(cf.len() == nc * 48 && (vss.is_none() || ct.len() == nc * 48), "coefficient encodings");  // len-guard
+    let ns = m * total;
+    let (mut x, mut y, mut xk, mut yk) = (vec![0u8; ns * 48], vec![0u8; ns * q * 48], vec![0u8; ns * ob],
+                                          vec![0u8; ns * q * ob]);
+    let pn = if vss.is_some() { 1 } else { 0 };
+    let (mut xt, mut yt, mut cm) = (vec![0u8; pn * ns * 48], vec![0u8; pn * ns * q * 48], vec![0u8; pn * nc * 97]);
+    assert!(x.len() == ns * 48 && y.len() == ns * q * 48 && xk.len() == ns * ob && yk.len() == ns * q * ob,
+            "share and verkey outputs");  // len-guard
+    assert!(vss.is_none() || (xt.len() == ns * 48 && yt.len() == ns * q * 48 && cm.len() == nc * 97),
+            "blinding share and commitment outputs");  // len-guard
+    let nm = std::ptr::null_mut::<u8>();
+    ctx.check(unsafe { cc_keygen_deal_batch(ctx.raw, m, q, t, total, cf.as_ptr(),
+                                            if vss.is_some() { ct.as_ptr() } else { null }, x.as_mut_ptr(),
+                                            y.as_mut_ptr(), if vss.is_some() { xt.as_mut_ptr() } else { nm },
+                                            if vss.is_some() { yt.as_mut_ptr() } else { nm },
+                                            if vss.is_some() { cm.as_mut_ptr() } else { nm }, xk.as_mut_ptr(),
+                                            yk.as_mut_ptr()) });
+    let fe = |b: &[u8], i: usize| FieldElement::from_bytes(&b[i * 48..(i + 1) * 48]).unwrap();
+    let og = |b: &[u8], i: usize| OtherGroup::from_bytes(&b[i * ob..(i + 1) * ob]).unwrap();
+    (0..m).map(|k| {
+        let signers = (0..total).map(|i| { let s = k * total + i; Signer {
+            id: i + 1,
+            sigkey: Sigkey { x: fe(&x, s), y: (0..q).map(|j| fe(&y, s * q + j)).collect() },
+            verkey: Verkey { X_tilde: og(&xk, s), Y_tilde: (0..q).map(|j| og(&yk, s * q + j)).collect() } } }).collect();
+        let sec = |p: usize| fe(&cf, (k * (q + 1) + p) * t);
+        let ped = vss.map(|_| (
+            (0..(q + 1) * t).map(|i| G1::from_bytes(&cm[(k * (q + 1) * t + i) * 97..(k * (q + 1) * t + i + 1) * 97])
+                                 .unwrap()).collect(),
+            (0..total).flat_map(|i| { let s = k * total + i;
+                let mut v = vec![fe(&xt, s)];
+                v.extend((0..q).map(|j| fe(&yt, s * q + j)));
+                v }).collect()));
+        (sec(0), (1..=q).map(sec).collect(), signers, ped)
     }).collect()
 }
 

@@ -158,6 +158,26 @@ extern "C" {
     pub fn cc_vss_verify_batch(ctx: *mut CcCtx, n: usize, t: usize, g: *const u8, h: *const u8,
                                commitments: *const u8, n_sets: usize, set_of: *const u32, ids: *const u64,
                                shares: *const u8, verdicts: *mut u8) -> c_int;
+    // keygen (keygen.rs:17-205): m trusted-party keygens per call, and the decentralized keygen's final sums;
+    // vss_g / vss_h and the Pedersen buffers may be null (Shamir)
+    pub fn cc_set_keygen_params(ctx: *mut CcCtx, g_tilde: *const u8, vss_g: *const u8, vss_h: *const u8,
+                                table_bits: c_int) -> c_int;
+    pub fn cc_keygen_deal_batch(ctx: *mut CcCtx, m: usize, q: usize, t: usize, total: usize, coeffs: *const u8,
+                                coeffs_t: *const u8, out_x: *mut u8, out_y: *mut u8, out_xt: *mut u8,
+                                out_yt: *mut u8, out_comm: *mut u8, out_x_tilde: *mut u8, out_y_tilde: *mut u8) -> c_int;
+    pub fn cc_keygen_deal_batch_device(ctx: *mut CcCtx, m: usize, q: usize, t: usize, total: usize,
+                                       d_coeffs: *const u8, d_coeffs_t: *const u8, d_out_x: *mut u8,
+                                       d_out_y: *mut u8, d_out_xt: *mut u8, d_out_yt: *mut u8, d_out_comm: *mut u8,
+                                       d_out_x_tilde: *mut u8, d_out_y_tilde: *mut u8, stream: *mut c_void) -> c_int;
+    pub fn cc_keygen_combine_batch(ctx: *mut CcCtx, m: usize, d: usize, q: usize, t: usize, total: usize,
+                                   x: *const u8, y: *const u8, xt: *const u8, yt: *const u8, comm: *const u8,
+                                   out_x: *mut u8, out_y: *mut u8, out_xt: *mut u8, out_yt: *mut u8,
+                                   out_comm: *mut u8, out_x_tilde: *mut u8, out_y_tilde: *mut u8) -> c_int;
+    pub fn cc_keygen_combine_batch_device(ctx: *mut CcCtx, m: usize, d: usize, q: usize, t: usize, total: usize,
+                                          d_x: *const u8, d_y: *const u8, d_xt: *const u8, d_yt: *const u8,
+                                          d_comm: *const u8, d_out_x: *mut u8, d_out_y: *mut u8, d_out_xt: *mut u8,
+                                          d_out_yt: *mut u8, d_out_comm: *mut u8, d_out_x_tilde: *mut u8,
+                                          d_out_y_tilde: *mut u8, stream: *mut c_void) -> c_int;
     pub fn cc_fixed_base_mul(ctx: *mut CcCtx, group: c_int, base: *const u8, n: usize, scalars: *const u8,
                              out: *mut u8) -> c_int;
     pub fn cc_last_timing(ctx: *const CcCtx, prep_ms: *mut f32, miller_ms: *mut f32, fexp_ms: *mut f32) -> c_int;
