@@ -1,6 +1,6 @@
 // C ABI implementation (include/coconut_hip.h): contexts, device tables, batch launches.
 // Host side of the MI355X engine; every compute step runs in the HIP kernels of kernels.hip /
-// aggregate.hip — there is no CPU fallback in this library.
+// aggregate.hip (launch.h) — there is no CPU fallback in this library.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -14,144 +14,10 @@
 #include <vector>
 
 #include "../../include/coconut_hip.h"
+#include "devbuf.h"
+#include "launch.h"
 #include "rlc_part.h"
 #include "slots.h"
-
-extern "C" {
-int cck_decode_points(int group, size_t n, const uint8_t* d_bytes, uint32_t* d_out, uint32_t* d_inf, hipStream_t st);
-int cck_build_table(int group, int nbases, int wbits, const uint32_t* d_bases, const uint32_t* d_inf, uint32_t* d_pw,
-                    uint32_t* d_table, int lazy_g2, hipStream_t st);
-int cck_gtilde_lines(const uint32_t* d_gtilde_aff, uint32_t* d_lines, hipStream_t st);
-int cck_lazy_form(size_t n, const uint32_t* d_in, uint32_t* d_out, hipStream_t st);
-int cck_subgroup(int group, size_t n, const uint8_t* d_bytes, uint8_t* d_status, hipStream_t st);
-int cck_hash_to_curve(int group, size_t n, const uint8_t* d_data, const uint64_t* d_offsets, uint8_t* d_out,
-                      uint32_t* d_fail, hipStream_t st);
-int cck_shake256_48(size_t n, const uint8_t* d_data, const uint64_t* d_offsets, uint8_t* d_out, hipStream_t st);
-size_t cck_sigreq_proof_bytes(int group, int k);
-int cck_vss_verify(size_t n, int t, const uint8_t* d_g, const uint8_t* d_h, const uint8_t* d_comms,
-                   const uint32_t* d_set_of, const uint64_t* d_ids, const uint8_t* d_shares, uint32_t* d_scratch,
-                   uint8_t* d_ok, hipStream_t st);
-int cck_blind_assemble(int group, size_t n, int q, int k, const uint8_t* d_cts, const uint8_t* d_h,
-                       const uint8_t* d_known, const uint8_t* d_x, const uint8_t* d_y, uint8_t* d_pts, uint32_t* d_sc,
-                       hipStream_t st);
-size_t cck_sigreq_scratch_words(int group, size_t n, int k);
-int cck_sigreq_verify(int group, size_t n, int k, const uint8_t* d_g, const uint8_t* d_hvec, const uint8_t* d_comm,
-                      const uint8_t* d_cts, const uint8_t* d_pk, const uint8_t* d_proof, const uint8_t* d_chal,
-                      const uint8_t* d_hpts, uint32_t* d_scratch, uint8_t* d_ok, uint8_t* d_verdicts, hipStream_t st);
-int cck_prep(int mode, size_t n, int q, const uint8_t* d_s1, const uint8_t* d_s2, const uint8_t* d_msgs,
-             const uint32_t* d_Xaff, uint32_t Xinf, const uint32_t* d_table, int wbits, const uint32_t* d_binf_fixed,
-             uint32_t* d_prep, uint32_t* d_flags, hipStream_t st);
-int cck_prep_wide(int mode, size_t n, int q, const uint8_t* d_s1, const uint8_t* d_s2, const uint8_t* d_msgs,
-                  const uint32_t* d_Xaff, uint32_t Xinf, const uint32_t* d_table, int wbits, const uint32_t* d_binf_fixed,
-                  uint32_t* d_prep, uint32_t* d_flags, hipStream_t st);
-size_t cck_prep_var_words(int mode, size_t n, size_t q);
-int cck_prep_var(int mode, size_t n, int q, const uint8_t* d_s1, const uint8_t* d_s2, const uint8_t* d_vkX,
-                 const uint8_t* d_vkY, const uint8_t* d_msgs, uint32_t* d_scratch, uint32_t* d_prep,
-                 uint32_t* d_flags, int wide, hipStream_t st);
-int cck_miller_lz_g2(int twin, size_t n, size_t pstride, const uint32_t* d_prep, const uint32_t* d_flags,
-                     const uint32_t* d_const, uint32_t* d_f, size_t fstride, size_t foff, uint32_t* d_qcheck,
-                     hipStream_t st);
-int cck_miller_lz_g1(int twin, size_t n, size_t pstride, const uint32_t* d_prep, const uint32_t* d_flags,
-                     const uint32_t* d_const, uint32_t* d_f, size_t fstride, size_t foff, uint32_t* d_qcheck,
-                     hipStream_t st);
-int cck_miller4_lz_g2(size_t n, size_t pstride, const uint32_t* d_prep, const uint32_t* d_flags, uint32_t* d_f,
-                      size_t fstride, size_t foff, uint32_t* d_qcheck, hipStream_t st);
-int cck_miller4_lz_g1(size_t n, size_t pstride, const uint32_t* d_prep, const uint32_t* d_flags, uint32_t* d_f,
-                      size_t fstride, size_t foff, uint32_t* d_qcheck, hipStream_t st);
-size_t cck_fold_words(int mode, size_t n);
-int cck_fold_pseudo();
-int cck_fold_window(int mode, size_t n, uint32_t* d_work, uint32_t* d_partial, hipStream_t st);
-int cck_fold(int mode, size_t n, const int8_t* d_dig, const uint32_t* d_pts, uint32_t* d_work, hipStream_t st);
-int cck_fold_fixed(int mode, int q, const uint32_t* d_table, int wbits, const uint32_t* d_binf, uint32_t* d_pw,
-                   uint8_t* d_finf, hipStream_t st);
-int cck_miller_wide(size_t n, const uint32_t* d_prep, const uint32_t* d_flags, uint32_t* d_f, size_t fstride,
-                    size_t foff, hipStream_t st);
-int cck_f12_reduce_wide(size_t n, const uint32_t* d_in, uint32_t* d_out, hipStream_t st);
-int cck_wide_pairs(int mode, size_t n, size_t ps, const uint32_t* d_prep, const uint32_t* d_flags,
-                   const uint32_t* d_gaff, uint32_t* d_wprep, uint32_t* d_wflags, hipStream_t st);
-int cck_fexp(size_t n, uint32_t* d_f, uint32_t* d_scratch, const uint32_t* d_flags, uint8_t* d_verdicts,
-             uint8_t* d_gt, size_t wide_max, hipStream_t st);
-int cck_lagrange(size_t n, size_t len, size_t t, const uint64_t* d_ids, uint32_t* d_l, hipStream_t st);
-int cck_h_input_canon(int group, size_t n, size_t len, int kn, uint8_t* d_data, hipStream_t st);
-
-size_t cck_straus_words(int group, size_t t);
-int cck_msm_straus(int group, size_t ntask, size_t t, const uint8_t* d_pts, size_t pt_stride, size_t pt_jstride,
-                   size_t pt_step, const uint32_t* d_l, size_t l_div, uint32_t* d_scratch, uint8_t* d_out,
-                   hipStream_t st);
-int cck_vk_agg_fixed(int group, size_t n, size_t len, size_t t, int q, const uint64_t* d_ids, const uint32_t* d_l,
-                     const uint64_t* d_iss_ids, int n_iss, const uint32_t* d_table, int wbits, const uint32_t* d_binf,
-                     uint8_t* d_outX, uint8_t* d_outY, uint32_t* d_err, hipStream_t st);
-int cck_copy_rows(size_t n, size_t sb, const uint8_t* d_src, size_t pitch, uint8_t* d_dst, hipStream_t st);
-int cck_fixed_mul(int group, size_t n, const uint8_t* d_ks, const uint32_t* d_table, uint32_t base_inf,
-                  uint8_t* d_out, hipStream_t st);
-int cck_prep_rlc(int mode, int part, size_t n, size_t ps, int q, uint64_t base_index, const uint32_t* d_key,
-                 const uint8_t* d_s1, const uint8_t* d_s2, const uint8_t* d_msgs, const uint32_t* d_table, int wbits,
-                 const uint32_t* d_binf, uint32_t* d_prep, uint32_t* d_flags, uint32_t* d_any, uint32_t* d_pts,
-                 int8_t* d_dig, hipStream_t st);
-int cck_rlc_reduce(size_t n, uint32_t* d_a, uint32_t* d_b, const uint32_t* d_any, uint32_t* d_partial,
-                   hipStream_t st);
-int cck_rlc_gather(int mode, size_t k, const uint32_t* d_parts, const uint32_t* d_pw, const uint8_t* d_finf,
-                   uint32_t* d_fw, size_t fs, uint32_t* d_prep, uint32_t* d_flags2, uint32_t* d_flag, hipStream_t st);
-int cck_prep_pok(int mode, size_t n, int q, int r, const uint8_t* d_s1, const uint8_t* d_s2, const uint8_t* d_J,
-                 const uint8_t* d_T, const uint8_t* d_resp, const uint8_t* d_chal, const uint8_t* d_rev_msgs,
-                 const uint32_t* d_rev_idx, const uint32_t* d_Xaff, uint32_t Xinf, const uint32_t* d_table, int wbits,
-                 const uint32_t* d_binf, uint32_t* d_prep, uint32_t* d_flags, uint32_t* d_jtab, hipStream_t st);
-int cck_prep_pok_rlc(int mode, size_t n, size_t ps, int q, int r, uint64_t base_index, const uint32_t* d_key,
-                     const uint8_t* d_J, const uint8_t* d_T, const uint8_t* d_resp, const uint8_t* d_chal,
-                     const uint8_t* d_rev_msgs, const uint32_t* d_rev_idx, const uint32_t* d_table, int wbits,
-                     const uint32_t* d_binf, uint32_t* d_prep, uint32_t* d_flags, uint32_t* d_any, uint32_t* d_jtab,
-                     hipStream_t st);
-int cck_prep_pok_wide(int mode, size_t n, int q, int r, const uint8_t* d_s1, const uint8_t* d_s2, const uint8_t* d_J,
-                 const uint8_t* d_T, const uint8_t* d_resp, const uint8_t* d_chal, const uint8_t* d_rev_msgs,
-                 const uint32_t* d_rev_idx, const uint32_t* d_Xaff, uint32_t Xinf, const uint32_t* d_table, int wbits,
-                 const uint32_t* d_binf, uint32_t* d_prep, uint32_t* d_flags, uint32_t* d_jtab, hipStream_t st);
-size_t cck_prep_pok_var_words(int mode, size_t n, size_t q);
-int cck_prep_pok_var(int mode, size_t n, int q, int r, const uint8_t* d_s1, const uint8_t* d_s2, const uint8_t* d_J,
-                     const uint8_t* d_T, const uint8_t* d_resp, const uint8_t* d_chal, const uint8_t* d_rev_msgs,
-                     const uint32_t* d_rev_idx, const uint8_t* d_vkX, const uint8_t* d_vkY, const uint32_t* d_gaff,
-                     uint32_t ginf, uint32_t* d_scratch, uint32_t* d_prep, uint32_t* d_flags, hipStream_t st);
-size_t cck_sigma_prime_words(int mode, size_t n);
-int cck_sigma_prime(int mode, size_t n, size_t rstride, const uint8_t* d_s1, const uint8_t* d_s2, const uint8_t* d_rnd,
-                    uint32_t* d_scratch, uint8_t* d_o1, uint8_t* d_o2, hipStream_t st);
-int cck_pok_commit(int mode, size_t n, int q, int r, const uint8_t* d_msgs, const uint8_t* d_rnd,
-                   const uint32_t* d_rev_idx, const uint32_t* d_table, int wbits, const uint32_t* d_binf, uint8_t* d_J,
-                   uint8_t* d_T, hipStream_t st);
-int cck_pok_responses(size_t n, int q, int r, const uint8_t* d_msgs, const uint8_t* d_rnd, const uint8_t* d_chal,
-                      const uint32_t* d_rev_idx, uint8_t* d_out, hipStream_t st);
-int cck_unblind_assemble(int group, size_t n, const uint8_t* d_c1, const uint8_t* d_c2, const uint8_t* d_sk,
-                         uint8_t* d_pts, uint32_t* d_sc, hipStream_t st);
-size_t cck_rq_table_words(int group, size_t n);
-size_t cck_rq_digit_bytes(size_t n, int k);
-int cck_rq_fixed(int group, size_t n, int q, int k, int init, const uint8_t* d_msgs, const uint8_t* d_rnd,
-                 const uint32_t* d_table, int wbits, const uint32_t* d_binf, uint8_t* d_long, uint8_t* d_out,
-                 hipStream_t st);
-int cck_rq_two_base(int group, size_t n, int q, int k, int init, const uint8_t* d_pk, const uint8_t* d_h,
-                    const uint8_t* d_msgs, const uint8_t* d_rnd, uint32_t* d_tab, int8_t* d_digs, uint8_t* d_out,
-                    hipStream_t st);
-int cck_rq_h_rows(int group, size_t n, int q, int k, const uint8_t* d_commitment, const uint8_t* d_msgs,
-                  uint8_t* d_data, uint64_t* d_offsets, hipStream_t st);
-size_t cck_iv_table_words(int group, size_t n, int k);
-size_t cck_iv_cdig_bytes(size_t n);
-size_t cck_iv_dig_bytes(size_t n, int k);
-size_t cck_iv_ok_bytes(size_t n, int k);
-int cck_iv_checks(int group, size_t n, int q, int k, const uint8_t* d_comm, const uint8_t* d_cts, const uint8_t* d_pk,
-                  const uint8_t* d_proof, const uint8_t* d_chal, const uint8_t* d_h, const uint32_t* d_table,
-                  int wbits, const uint32_t* d_binf, uint32_t* d_tab, int8_t* d_cdig, int8_t* d_digs, uint8_t* d_ok,
-                  hipStream_t st);
-int cck_sigreq_combine(int group, size_t n, int k, const uint8_t* d_proof, const uint8_t* d_ok, uint8_t* d_verdicts,
-                       hipStream_t st);
-int cck_rq_responses(int group, size_t n, int q, int k, const uint8_t* d_msgs, const uint8_t* d_rnd,
-                     const uint8_t* d_blind, const uint8_t* d_sk, const uint8_t* d_chal, uint8_t* d_proofs,
-                     hipStream_t st);
-// keygen.hip
-int cck_kg_eval(size_t m, int q, int t, int total, const uint8_t* d_cf, const uint8_t* d_ct, uint8_t* d_x, uint8_t* d_y,
-                uint8_t* d_xt, uint8_t* d_yt, hipStream_t st);
-int cck_kg_commit(size_t n, const uint8_t* d_cf, const uint8_t* d_ct, const uint32_t* d_table, int wbits,
-                  const uint32_t* d_binf, uint8_t* d_out, hipStream_t st);
-int cck_kg_derive(int group, size_t nrow, int q, const uint8_t* d_x, const uint8_t* d_y, const uint32_t* d_table,
-                  int wbits, const uint32_t* d_binf, uint8_t* d_X, uint8_t* d_Y, hipStream_t st);
-int cck_kg_sum(int g1, size_t m, size_t inner, int d, const uint8_t* d_in, uint8_t* d_out, hipStream_t st);
-}
 
 namespace {
 
@@ -169,32 +35,50 @@ static size_t free_hbm() {
     }
     return fr;
 }
+// The window width of the issuer, request and keygen tables (bytes(w) bytes at w bits): the forced width, else the
+// widest of 16 / 13 / 12 / 10 bits that fits cap and half the free HBM, else 8.  Called with the old tables released,
+// so their memory counts as free and identical calls pick the same width.
+template <class Bytes>
+static int pick_table_bits(int forced, double cap, Bytes bytes) {
+    if (forced) return forced;
+    const double budget = std::min(cap, 0.5 * (double)free_hbm());
+    for (int cand : {16, 13, 12, 10})
+        if ((double)bytes(cand) <= budget) return cand;
+    return 8;
+}
+// ... and their allocation (alloc(w): true when done).  A width whose tables exceed 0.9 of the free HBM is refused up
+// front (see rebuild_tables); a refused or failed width falls back to 8 bits unless it was forced or was 8 already.
+// Returns the width allocated, 0 on failure.
+template <class Bytes, class Alloc>
+static int alloc_tables(int wb, bool forced, Bytes bytes, Alloc alloc) {
+    const double fr = (double)free_hbm();
+    if (!(fr > 0 && (double)bytes(wb) > 0.9 * fr) && alloc(wb)) return wb;
+    (void)hipGetLastError();  // clear a failed allocation's error
+    return forced || wb == 8 || !alloc(8) ? 0 : 8;
+}
 constexpr size_t PREP_SLOTS = cc::slots::kPrepSlots;  // soa.h
 // default HBM budget of a context's shared-verkey tables (wider: cc_set_table_bits)
 constexpr double kVkTableBudget = 4.0 * (double)(1ull << 30);
 
-struct DevBuf {
-    void* p = nullptr;
-    size_t bytes = 0;
-    int ensure(size_t want) {
-        if (want <= bytes) return 0;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        bytes = 0;
-        if (hipMalloc(&p, want) != hipSuccess) return -1;
-        bytes = want;
-        return 0;
+// The device policy of the owned buffers and of the host forms' sequence (devbuf.h)
+struct HipMem {
+    using Stream = hipStream_t;
+    static void* alloc(size_t n) {
+        void* p = nullptr;
+        return hipMalloc(&p, n) == hipSuccess ? p : nullptr;
     }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        bytes = 0;
+    static void free(void* p) { (void)hipFree(p); }
+    static int h2d(void* d, const void* h, size_t n, hipStream_t st) {
+        return hipMemcpyAsync(d, h, n, hipMemcpyHostToDevice, st) == hipSuccess ? 0 : -1;
     }
-    template <class T>
-    T* as() const {
-        return reinterpret_cast<T*>(p);
+    static int d2h(void* h, const void* d, size_t n, hipStream_t st) {
+        return hipMemcpyAsync(h, d, n, hipMemcpyDeviceToHost, st) == hipSuccess ? 0 : -1;
     }
+    static int zero(void* d, size_t n, hipStream_t st) { return hipMemsetAsync(d, 0, n, st) == hipSuccess ? 0 : -1; }
+    static int sync(hipStream_t st) { return hipStreamSynchronize(st) == hipSuccess ? 0 : -1; }
 };
+using DevBuf = cc::dev::BasicDevBuf<HipMem>;
+using HostForm = cc::dev::HostForm<HipMem>;
 
 // The device policy of the slot bookkeeping (slots.h): hipMalloc'd buffers, HIP events and streams.
 struct HipDev {
@@ -399,6 +283,22 @@ struct StreamOrder {
     }
 };
 
+// The next concurrent slot (round-robin, slots.h Pool): its workspaces grown to the batch's sizes once
+// its last batch is done, and stream st ordered after the context stream's queued work (tables, params,
+// other entry points) and after that last batch.  f(k, w) queues the batch on slot k's workspaces w; a
+// SlotFence records the slot's completion on st on every exit.
+template <class F>
+static cc_status on_slot(cc_ctx* c, hipStream_t st, const cc::slots::Sizes& sz, F f) {
+    const int k = c->pool.take();
+    const VerifyWork w = c->pool.recs[(size_t)k].w;
+    const int rc = c->pool.begin(c->dev, k, sz, st, c->stream, c->ev_order);
+    if (rc) return rc == -2 ? CC_ERR_STATE : CC_ERR_HIP;
+    SlotFence fence(c->pool, c->dev, k, st);
+    const cc_status s = f(k, w);
+    if (s) return s;
+    return fence.close() ? CC_ERR_HIP : CC_OK;
+}
+
 // mode 0 (SigG2): d_const = g~ affine G1 in the lazy R' form (24 words); mode 1 (SigG1): g~ Miller lines
 // (68 x 72 words).
 // Pairing kernels run one credential per lane pair (tower_pl.h).  Miller values go to SoA elements
@@ -511,28 +411,12 @@ cc_status cc_ctx_destroy(cc_ctx* c) {
     (void)hipSetDevice(c->device);
     drain_slots(c);
     (void)hipStreamSynchronize(c->stream);
-    for (VerifySlot* v : c->vslots) {
-        v->each([](DevBuf& b) { b.release(); });
-        delete v;
-    }
+    for (VerifySlot* v : c->vslots) delete v;
     c->vslots.clear();
     for (auto& r : c->pool.recs)
         if (r.done) (void)hipEventDestroy(r.done);
     c->pool.recs.clear();
     for (Staging& g : c->stage) g.release();
-    DevBuf* bufs[] = {&c->gtilde_aff, &c->gtilde_lines, &c->gtilde_lz, &c->vk_aff, &c->vk_inf, &c->table, &c->table_inf,
-                      &c->in_s1, &c->in_s2, &c->in_msgs, &c->in_vkX, &c->in_vkY, &c->prep, &c->flags,
-                      &c->fbuf, &c->scratch, &c->verdicts, &c->gt, &c->vkb, &c->lag, &c->wide_prep, &c->wide_flags, &c->wide_f,
-                      &c->rlc_key, &c->rlc_any, &c->rlc_part, &c->rlc_flag, &c->rlc_accept, &c->fin_f, &c->fin_scratch, &c->fin_prep, &c->fin_flags2, &c->fin_part, &c->pok_idx, &c->rlc_gath,
-                      &c->rlc_pts, &c->rlc_dig, &c->rlc_work, &c->rlc_pw, &c->rlc_finf,
-                      &c->iss_ids, &c->iss_aff, &c->iss_inf, &c->iss_table, &c->agg_scratch, &c->dev_err,
-                      &c->prove_idx, &c->prove_scratch, &c->rq_aff, &c->rq_inf, &c->rq_table, &c->rq_tab, &c->rq_dig,
-                      &c->rq_hdata, &c->rq_hoff, &c->rq_fail, &c->iv_h, &c->iv_tab, &c->iv_cdig, &c->iv_dig, &c->iv_ok,
-                      &c->bs_pts, &c->bs_sc, &c->bs_out, &c->bs_xy, &c->kg_gt_aff, &c->kg_gt_inf, &c->kg_gt_table,
-                      &c->kg_gh_aff, &c->kg_gh_inf, &c->kg_gh_table};
-    for (auto* b : bufs) b->release();
-    for (auto& b : c->in_aux) b.release();
-    for (auto& b : c->kg_io) b.release();
     for (auto& e : c->ev) if (e) (void)hipEventDestroy(e);
     if (c->ev_order) (void)hipEventDestroy(c->ev_order);
     if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
@@ -540,7 +424,7 @@ cc_status cc_ctx_destroy(cc_ctx* c) {
     if (c->ev_fin) (void)hipEventDestroy(c->ev_fin);
     if (c->side) (void)hipStreamDestroy(c->side);
     (void)hipStreamDestroy(c->stream);
-    delete c;
+    delete c;  // frees every device buffer the context owns (DevBuf)
     return CC_OK;
 }
 
@@ -571,22 +455,21 @@ static cc_status decode_points_host(cc_ctx* c, int group, size_t n, const uint8_
     size_t eb = group == 1 ? 97 : 192;
     DevBuf tmp;
     if (tmp.ensure(eb * n + 16)) return CC_ERR_HIP;
-    HIPCK(hipMemcpyAsync(tmp.p, bytes, eb * n, hipMemcpyHostToDevice, c->stream));
-    KCK(cck_decode_points(group, n, tmp.as<uint8_t>(), d_out, d_inf, c->stream));
-    HIPCK(hipStreamSynchronize(c->stream));
-    tmp.release();
-    return CC_OK;
+    HostForm f(c->stream);
+    f.up(tmp, bytes, eb * n);
+    f.launch([&] { return cck_decode_points(group, n, tmp.as<uint8_t>(), d_out, d_inf, c->stream); });
+    return f.finish();
 }
 
 static cc_status subgroup_host(cc_ctx* c, int group, size_t n, const uint8_t* bytes, uint8_t* status) {
     size_t eb = group == 1 ? 97 : 192;
     DevBuf tmp, st;
     if (tmp.ensure(eb * n + 16) || st.ensure(n + 16)) return CC_ERR_HIP;
-    HIPCK(hipMemcpyAsync(tmp.p, bytes, eb * n, hipMemcpyHostToDevice, c->stream));
-    KCK(cck_subgroup(group, n, tmp.as<uint8_t>(), st.as<uint8_t>(), c->stream));
-    HIPCK(hipMemcpyAsync(status, st.p, n, hipMemcpyDeviceToHost, c->stream));
-    HIPCK(hipStreamSynchronize(c->stream));
-    return CC_OK;
+    HostForm f(c->stream);
+    f.up(tmp, bytes, eb * n);
+    f.launch([&] { return cck_subgroup(group, n, tmp.as<uint8_t>(), st.as<uint8_t>(), c->stream); });
+    f.down(status, st, n);
+    return f.finish();
 }
 
 // Shared-verkey tables: by default the widest of 22 / 20 / 18 / 16 / 14 / 12 / 10-bit windows whose q + 2
@@ -646,7 +529,6 @@ static cc_status rebuild_tables(cc_ctx* c) {
     KCK(cck_fold_fixed(c->mode, (int)c->q, c->table.as<uint32_t>(), c->wbits, c->table_inf.as<uint32_t>(),
                        c->rlc_pw.as<uint32_t>(), c->rlc_finf.as<uint8_t>(), c->stream));
     HIPCK(hipStreamSynchronize(c->stream));
-    pw.release();
     return CC_OK;
 }
 
@@ -695,7 +577,6 @@ cc_status cc_set_params(cc_ctx* c, const uint8_t* g_tilde) {
     if (s) return s;
     HIPCK(hipMemcpy(&c->gtilde_inf, inf.p, 4, hipMemcpyDeviceToHost));
     c->gtilde_bytes.assign(g_tilde, g_tilde + oth_bytes(c->mode));
-    inf.release();
     if (c->mode == 1) {
         if (c->gtilde_lines.ensure(68 * 72 * 4)) return CC_ERR_HIP;
         KCK(cck_gtilde_lines(c->gtilde_aff.as<uint32_t>(), c->gtilde_lines.as<uint32_t>(), c->stream));
@@ -843,6 +724,19 @@ static cc_status launch_miller(cc_ctx* c, const VerifyWork& w, size_t n, hipStre
     KCK(cck_miller(c->mode, n, w.prep->as<uint32_t>(), w.flags->as<uint32_t>(), cst, w.fbuf->as<uint32_t>(), st));
     return CC_OK;
 }
+// after a prep (phase 0 of the timing): the Miller loops and the final exponentiation of the n values
+static cc_status launch_pairings(cc_ctx* c, const VerifyWork& w, size_t n, uint8_t* d_verdicts, uint8_t* d_gt,
+                                 hipStream_t st) {
+    if (c->timing) (void)hipEventRecord(c->ev[1], st);
+    cc_status ms = launch_miller(c, w, n, st);
+    if (ms) return ms;
+    if (c->timing) (void)hipEventRecord(c->ev[2], st);
+    // n <= kFexpWideMax: one wave per credential (k_fexp1, its chain in w.scratch: 72 x 12 x n words)
+    KCK(cck_fexp(n, w.fbuf->as<uint32_t>(), w.scratch->as<uint32_t>(), w.flags->as<uint32_t>(), d_verdicts, d_gt,
+                 kFexpWideMax, st));
+    if (c->timing) (void)hipEventRecord(c->ev[3], st);
+    return CC_OK;
+}
 static cc_status launch_verify(cc_ctx* c, const VerifyWork& w, size_t n, size_t q, const uint8_t* d_s1,
                                const uint8_t* d_s2, const uint8_t* d_msgs, const uint8_t* d_vkX, const uint8_t* d_vkY,
                                uint8_t* d_verdicts, uint8_t* d_gt, hipStream_t st) {
@@ -855,15 +749,7 @@ static cc_status launch_verify(cc_ctx* c, const VerifyWork& w, size_t n, size_t 
                                                        c->vk_aff.as<uint32_t>(), c->X_inf, c->table.as<uint32_t>(),
                                                        c->wbits, c->table_inf.as<uint32_t>(), w.prep->as<uint32_t>(),
                                                        w.flags->as<uint32_t>(), st));
-    if (c->timing) (void)hipEventRecord(c->ev[1], st);
-    cc_status ms = launch_miller(c, w, n, st);
-    if (ms) return ms;
-    if (c->timing) (void)hipEventRecord(c->ev[2], st);
-    // n <= kFexpWideMax: one wave per credential (k_fexp1, its chain in w.scratch: 72 x 12 x n words)
-    KCK(cck_fexp(n, w.fbuf->as<uint32_t>(), w.scratch->as<uint32_t>(), w.flags->as<uint32_t>(), d_verdicts, d_gt,
-                 kFexpWideMax, st));
-    if (c->timing) (void)hipEventRecord(c->ev[3], st);
-    return CC_OK;
+    return launch_pairings(c, w, n, d_verdicts, d_gt, st);
 }
 
 static void collect_timing(cc_ctx* c) {
@@ -872,42 +758,34 @@ static void collect_timing(cc_ctx* c) {
     for (int k = 0; k < 3; k++) (void)hipEventElapsedTime(&c->last_ms[k], c->ev[k], c->ev[k + 1]);
 }
 
-// The next concurrent slot (round-robin, slots.h Pool): its workspaces grown to the batch's sizes once
-// its last batch is done, and stream st ordered after the context stream's queued work (tables, params,
-// other entry points) and after that last batch.  The caller holds a SlotFence that records the slot's
-// completion on st on every exit.
-static cc_status slot_begin(cc_ctx* c, hipStream_t st, const cc::slots::Sizes& sz, int& k, VerifyWork& w) {
-    k = c->pool.take();
-    w = c->pool.recs[(size_t)k].w;
-    const int rc = c->pool.begin(c->dev, k, sz, st, c->stream, c->ev_order);
-    return rc == -2 ? CC_ERR_STATE : rc ? CC_ERR_HIP : CC_OK;
-}
-
 // the *_device verify calls: with one slot, ordered against everything on the context (StreamOrder);
 // with K > 1 (cc_set_concurrency), on the next slot round-robin, ordered only after the context
 // stream's queued work (tables, params) and that slot's previous batch.
 static cc_status verify_device(cc_ctx* c, size_t n, size_t q, const uint8_t* d_s1, const uint8_t* d_s2,
                                const uint8_t* d_msgs, const uint8_t* d_vkX, const uint8_t* d_vkY, uint8_t* d_verdicts,
-                               uint8_t* d_gt, hipStream_t st) {
+                               uint8_t* d_gt, void* stream) {
+    if (n > kMaxBatch) return CC_ERR_DECODE;
+    if (!n) return CC_OK;
+    HIPCK(hipSetDevice(c->device));
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
     const size_t vkw = d_vkX ? cck_prep_var_words(c->mode, n, q) * 4 : 0;
+    cc_status s;
     if (c->concurrency <= 1) {
-        cc_status s = ensure_work(c, n);
+        s = ensure_work(c, n);
         if (s) return s;
         if (d_vkX && c->vkb.bytes < vkw) drain_slots(c);  // slot 0's batch may still read it
         StreamOrder order(c, st);
         if (d_vkX && c->vkb.ensure(vkw)) return CC_ERR_HIP;
-        return launch_verify(c, ctx_work(c), n, q, d_s1, d_s2, d_msgs, d_vkX, d_vkY, d_verdicts, d_gt, st);
+        s = launch_verify(c, ctx_work(c), n, q, d_s1, d_s2, d_msgs, d_vkX, d_vkY, d_verdicts, d_gt, st);
+    } else {
+        // the slot sizes its own workspaces (slot 0's too): no ensure_work, which would grow slot 0 for a
+        // batch landing on another slot and drain every slot in flight
+        s = on_slot(c, st, cc::slots::verify_sizes(n, vkw, 0, 0), [&](int, const VerifyWork& w) {
+            return launch_verify(c, w, n, q, d_s1, d_s2, d_msgs, d_vkX, d_vkY, d_verdicts, d_gt, st);
+        });
     }
-    // the slot sizes its own workspaces (slot 0's too): no ensure_work, which would grow slot 0 for a
-    // batch landing on another slot and drain every slot in flight
-    int k = 0;
-    VerifyWork w;
-    cc_status s = slot_begin(c, st, cc::slots::verify_sizes(n, vkw, 0, 0), k, w);
-    if (s) return s;
-    SlotFence fence(c->pool, c->dev, k, st);
-    s = launch_verify(c, w, n, q, d_s1, d_s2, d_msgs, d_vkX, d_vkY, d_verdicts, d_gt, st);
-    if (s) return s;
-    return fence.close() ? CC_ERR_HIP : CC_OK;
+    if (!s && c->timing) collect_timing(c);
+    return s;
 }
 
 cc_status cc_set_concurrency(cc_ctx* c, int slots) {
@@ -925,7 +803,6 @@ cc_status cc_set_concurrency(cc_ctx* c, int slots) {
     while ((int)c->vslots.size() > slots - 1) {
         VerifySlot* v = c->vslots.back();
         c->vslots.pop_back();
-        v->each([](DevBuf& b) { b.release(); });
         delete v;
         if (c->pool.recs.back().done) (void)hipEventDestroy(c->pool.recs.back().done);
         c->pool.recs.pop_back();
@@ -959,14 +836,7 @@ cc_status cc_verify_batch_device(cc_ctx* c, size_t n, size_t q, const uint8_t* d
     if (!c || (n && (!d_s1 || !d_s2 || !d_verdicts))) return CC_ERR_DECODE;
     if (!c->have_params || !c->have_vk) return CC_ERR_STATE;
     if (q != c->q) return CC_ERR_LEN;
-    if (n > kMaxBatch) return CC_ERR_DECODE;
-    if (!n) return CC_OK;
-    HIPCK(hipSetDevice(c->device));
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
-    cc_status s = verify_device(c, n, q, d_s1, d_s2, d_msgs, nullptr, nullptr, d_verdicts, d_gt, st);
-    if (s) return s;
-    if (c->timing) collect_timing(c);
-    return CC_OK;
+    return verify_device(c, n, q, d_s1, d_s2, d_msgs, nullptr, nullptr, d_verdicts, d_gt, stream);
 }
 
 cc_status cc_verify_batch_pervk_device(cc_ctx* c, size_t n, size_t q, const uint8_t* d_s1, const uint8_t* d_s2,
@@ -976,14 +846,7 @@ cc_status cc_verify_batch_pervk_device(cc_ctx* c, size_t n, size_t q, const uint
     if (!c || q > 4096 || (n && (!d_s1 || !d_s2 || !d_vkX || !d_verdicts || (q && (!d_msgs || !d_vkY)))))
         return CC_ERR_DECODE;
     if (!c->have_params) return CC_ERR_STATE;
-    if (n > kMaxBatch) return CC_ERR_DECODE;
-    if (!n) return CC_OK;
-    HIPCK(hipSetDevice(c->device));
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
-    cc_status s = verify_device(c, n, q, d_s1, d_s2, d_msgs, d_vkX, d_vkY, d_verdicts, d_gt, st);
-    if (s) return s;
-    if (c->timing) collect_timing(c);
-    return CC_OK;
+    return verify_device(c, n, q, d_s1, d_s2, d_msgs, d_vkX, d_vkY, d_verdicts, d_gt, stream);
 }
 
 
@@ -1003,6 +866,12 @@ struct RlcWork {
 };
 static RlcWork ctx_rlc_work(cc_ctx* c) {
     return {&c->prep, &c->flags, &c->fbuf, &c->scratch, &c->rlc_key, &c->rlc_any, &c->rlc_pts, &c->rlc_dig, &c->rlc_work};
+}
+// concurrency slot k's: slot 0 is the context's own
+static RlcWork slot_rlc_work(cc_ctx* c, int k) {
+    if (!k) return ctx_rlc_work(c);
+    VerifySlot* sl = c->vslots[(size_t)k - 1];
+    return {&sl->prep, &sl->flags, &sl->fbuf, &sl->scratch, &sl->rkey, &sl->rany, &sl->rpts, &sl->rdig, &sl->rwork};
 }
 // sizes for n credentials; a concurrency slot whose buffers must grow waits for its last batch first
 // (scr_min: the PoK partial's tables of d J, which share the scratch with the product tree)
@@ -1157,19 +1026,12 @@ cc_status cc_rlc_partial_device(cc_ctx* c, size_t n, size_t q, uint64_t base_ind
     hipStream_t st = stream ? (hipStream_t)stream : c->stream;
     if (!n) return write_neutral_partial(d_partial, st);
     if (c->concurrency > 1) {  // the next concurrency slot (cc_set_concurrency): its own workspaces
-        int k = 0;
-        VerifyWork w;
-        cc_status s = slot_begin(c, st, cc::slots::verify_sizes(n, 0, 0, 0), k, w);
-        if (s) return s;
-        SlotFence fence(c->pool, c->dev, k, st);
-        VerifySlot* sl = k ? c->vslots[(size_t)k - 1] : nullptr;
-        RlcWork r = sl ? RlcWork{&sl->prep, &sl->flags, &sl->fbuf, &sl->scratch, &sl->rkey, &sl->rany, &sl->rpts,
-                                 &sl->rdig, &sl->rwork}
-                       : ctx_rlc_work(c);
-        if (rlc_ensure(c, r, n, &c->pool.recs[(size_t)k])) return CC_ERR_HIP;
-        s = launch_rlc_partial(c, r, n, q, base_index, seed32, d_s1, d_s2, d_msgs, d_partial, st, &c->stage[(size_t)k]);
-        if (s) return s;
-        return fence.close() ? CC_ERR_HIP : CC_OK;
+        return on_slot(c, st, cc::slots::verify_sizes(n, 0, 0, 0), [&](int k, const VerifyWork&) -> cc_status {
+            RlcWork r = slot_rlc_work(c, k);
+            if (rlc_ensure(c, r, n, &c->pool.recs[(size_t)k])) return CC_ERR_HIP;
+            return launch_rlc_partial(c, r, n, q, base_index, seed32, d_s1, d_s2, d_msgs, d_partial, st,
+                                      &c->stage[(size_t)k]);
+        });
     }
     drain_slots(c);  // concurrent batches (cc_set_concurrency) may still use the buffers sized below
     cc_status s = ensure_work(c, n);
@@ -1310,18 +1172,29 @@ cc_status cc_fixed_base_mul(cc_ctx* c, int group, const uint8_t* base, size_t n,
     if (s) return s;
     uint32_t binf = 0;
     HIPCK(hipMemcpy(&binf, inf.p, 4, hipMemcpyDeviceToHost));
-    KCK(cck_build_table(group, 1, 8, aff.as<uint32_t>(), inf.as<uint32_t>(), pw.as<uint32_t>(), table.as<uint32_t>(), 0,
-                        st));
-    HIPCK(hipMemcpyAsync(ks.p, scalars, n * 48, hipMemcpyHostToDevice, st));
-    KCK(cck_fixed_mul(group, n, ks.as<uint8_t>(), table.as<uint32_t>(), binf, o.as<uint8_t>(), st));
-    HIPCK(hipMemcpyAsync(out, o.p, n * eb, hipMemcpyDeviceToHost, st));
-    HIPCK(hipStreamSynchronize(st));
-    return CC_OK;
+    HostForm f(st);
+    f.up(ks, scalars, n * 48);
+    f.launch([&]() -> cc_status {
+        KCK(cck_build_table(group, 1, 8, aff.as<uint32_t>(), inf.as<uint32_t>(), pw.as<uint32_t>(), table.as<uint32_t>(),
+                            0, st));
+        KCK(cck_fixed_mul(group, n, ks.as<uint8_t>(), table.as<uint32_t>(), binf, o.as<uint8_t>(), st));
+        return CC_OK;
+    });
+    f.down(out, o, n * eb);
+    return f.finish();
 }
 
 // Lagrange-weighted MSMs: windowed Straus over variable bases (aggregate.hip k_msm_straus)
 static cc_status agg_scratch(cc_ctx* c, int group, size_t ntask, size_t t) {
     return c->agg_scratch.ensure(ntask * cck_straus_words(group, t) * 4 + 64) ? CC_ERR_HIP : CC_OK;
+}
+
+// the aggregation forms' checks after the NULL checks, in the header's order; the reference asserts
+// sigs.len() >= threshold and reads sigs[0] (signature.rs:449-452)
+static cc_status agg_checks(size_t n, size_t len, size_t t) {
+    if (len > kMaxIds) return CC_ERR_DECODE;
+    if (len < t || len == 0) return CC_ERR_THRESHOLD;
+    return n > kMaxBatch ? CC_ERR_DECODE : CC_OK;
 }
 
 static cc_status launch_sig_aggregate(cc_ctx* c, size_t n, size_t len, size_t t, const uint64_t* d_ids,
@@ -1348,9 +1221,7 @@ cc_status cc_signature_aggregate_batch_device(cc_ctx* c, size_t n, size_t len, s
                                               uint8_t* d_out_s2, void* stream) {
     c = primary(c);  // a device set forwards to its first device
     if (!c || (n && (!d_ids || !d_s1 || !d_s2 || !d_out_s1 || !d_out_s2))) return CC_ERR_DECODE;
-    if (len > kMaxIds) return CC_ERR_DECODE;
-    if (len < t || len == 0) return CC_ERR_THRESHOLD;  // reference: assert!(sigs.len() >= threshold)
-    if (n > kMaxBatch) return CC_ERR_DECODE;
+    if (cc_status e = agg_checks(n, len, t)) return e;
     if (!n) return CC_OK;
     HIPCK(hipSetDevice(c->device));
     hipStream_t st = stream ? (hipStream_t)stream : c->stream;
@@ -1365,9 +1236,7 @@ cc_status cc_signature_aggregate_batch(cc_ctx* c, size_t n, size_t len, size_t t
                                        const uint8_t* s1, const uint8_t* s2, uint8_t* out_s1, uint8_t* out_s2) {
     c = primary(c);  // a device set forwards to its first device
     if (!c || (n && (!ids || !s1 || !s2 || !out_s1 || !out_s2))) return CC_ERR_DECODE;
-    if (len > kMaxIds) return CC_ERR_DECODE;
-    if (len < t || len == 0) return CC_ERR_THRESHOLD;  // reference: assert!(sigs.len() >= threshold) + sigs[0]
-    if (n > kMaxBatch) return CC_ERR_DECODE;
+    if (cc_status e = agg_checks(n, len, t)) return e;
     if (!n) return CC_OK;
     HIPCK(hipSetDevice(c->device));
     size_t sb = (size_t)sig_bytes(c->mode);
@@ -1396,9 +1265,7 @@ cc_status cc_verkey_aggregate_batch(cc_ctx* c, size_t n, size_t len, size_t t, s
                                     const uint8_t* X, const uint8_t* Y, uint8_t* outX, uint8_t* outY) {
     c = primary(c);  // a device set forwards to its first device
     if (!c || (n && (!ids || !X || !outX || (q && (!Y || !outY))))) return CC_ERR_DECODE;
-    if (len > kMaxIds) return CC_ERR_DECODE;
-    if (len < t || len == 0) return CC_ERR_THRESHOLD;
-    if (n > kMaxBatch) return CC_ERR_DECODE;
+    if (cc_status e = agg_checks(n, len, t)) return e;
     if (!n) return CC_OK;
     HIPCK(hipSetDevice(c->device));
     size_t ob = (size_t)oth_bytes(c->mode);
@@ -1442,17 +1309,44 @@ cc_status cc_subgroup_check(cc_ctx* c, int group, size_t n, const uint8_t* point
 }
 
 // ---------------------------------------------------------------- hash-to-curve (§8(f) row 2)
-static cc_status stage_messages(cc_ctx* c, size_t n, const uint8_t* data, const uint64_t* offsets, DevBuf& d_data,
-                                DevBuf& d_off) {
+// the checks of a message list (data, offsets[n + 1]) and its device buffers; the caller uploads
+// offsets[n] bytes of data and the n + 1 offsets
+static cc_status stage_messages(size_t n, const uint8_t* data, const uint64_t* offsets, DevBuf& d_data, DevBuf& d_off) {
     if (offsets[0] != 0) return CC_ERR_DECODE;
     for (size_t i = 0; i < n; i++)
         if (offsets[i + 1] < offsets[i]) return CC_ERR_DECODE;
     const size_t total = offsets[n];
     if (total && !data) return CC_ERR_DECODE;
     if (d_data.ensure(total + 16) || d_off.ensure((n + 1) * 8)) return CC_ERR_HIP;
-    if (total) HIPCK(hipMemcpyAsync(d_data.p, data, total, hipMemcpyHostToDevice, c->stream));
-    HIPCK(hipMemcpyAsync(d_off.p, offsets, (n + 1) * 8, hipMemcpyHostToDevice, c->stream));
     return CC_OK;
+}
+
+// from_msg_hash of the n messages (data, offsets[n + 1]) into d_out, and to host_out if given.  canon_len != 0: the
+// rows are compute_h inputs of that length with kn known messages; the reference hashes commitment.to_bytes() and
+// the known messages' to_bytes(), so they are made canonical first.
+static cc_status hash_rows(cc_ctx* c, int group, size_t n, const uint8_t* data, const uint64_t* offsets, size_t canon_len,
+                           int kn, DevBuf& d_out, uint8_t* host_out) {
+    const size_t eb = group == 1 ? 97 : 192;
+    DevBuf d_data, d_off, d_fail;
+    cc_status s = stage_messages(n, data, offsets, d_data, d_off);
+    if (s) return s;
+    if (d_out.ensure(n * eb) || d_fail.ensure(4)) return CC_ERR_HIP;
+    uint32_t fail = 0;
+    HostForm f(c->stream);
+    f.up(d_data, data, offsets[n]);
+    f.up(d_off, offsets, (n + 1) * 8);
+    f.launch([&]() -> cc_status {
+        HIPCK(hipMemsetAsync(d_fail.p, 0, 4, c->stream));
+        if (canon_len) KCK(cck_h_input_canon(group, n, canon_len, kn, d_data.as<uint8_t>(), c->stream));
+        KCK(cck_hash_to_curve(group, n, d_data.as<uint8_t>(), d_off.as<uint64_t>(), d_out.as<uint8_t>(),
+                              d_fail.as<uint32_t>(), c->stream));
+        return CC_OK;
+    });
+    f.down(host_out, d_out, host_out ? n * eb : 0);
+    f.down(&fail, d_fail, 4);
+    s = f.finish();
+    if (s) return s;
+    return fail ? CC_ERR_DECODE : CC_OK;  // 4,096 failed tries (probability ~2^-4096)
 }
 
 cc_status cc_hash_to_curve(cc_ctx* c, int group, size_t n, const uint8_t* data, const uint64_t* offsets, uint8_t* out) {
@@ -1461,19 +1355,8 @@ cc_status cc_hash_to_curve(cc_ctx* c, int group, size_t n, const uint8_t* data, 
     if (n > kMaxBatch) return CC_ERR_DECODE;
     if (!n) return CC_OK;
     HIPCK(hipSetDevice(c->device));
-    const size_t eb = group == 1 ? 97 : 192;
-    DevBuf d_data, d_off, d_out, d_fail;
-    cc_status s = stage_messages(c, n, data, offsets, d_data, d_off);
-    if (s) return s;
-    if (d_out.ensure(n * eb) || d_fail.ensure(4)) return CC_ERR_HIP;
-    HIPCK(hipMemsetAsync(d_fail.p, 0, 4, c->stream));
-    KCK(cck_hash_to_curve(group, n, d_data.as<uint8_t>(), d_off.as<uint64_t>(), d_out.as<uint8_t>(),
-                          d_fail.as<uint32_t>(), c->stream));
-    uint32_t fail = 0;
-    HIPCK(hipMemcpyAsync(out, d_out.p, n * eb, hipMemcpyDeviceToHost, c->stream));
-    HIPCK(hipMemcpyAsync(&fail, d_fail.p, 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCK(hipStreamSynchronize(c->stream));
-    return fail ? CC_ERR_DECODE : CC_OK;  // 4,096 failed tries (probability ~2^-4096)
+    DevBuf d_out;
+    return hash_rows(c, group, n, data, offsets, 0, 0, d_out, out);
 }
 
 cc_status cc_hash_msg(cc_ctx* c, size_t n, const uint8_t* data, const uint64_t* offsets, uint8_t* out48) {
@@ -1483,13 +1366,17 @@ cc_status cc_hash_msg(cc_ctx* c, size_t n, const uint8_t* data, const uint64_t* 
     if (!n) return CC_OK;
     HIPCK(hipSetDevice(c->device));
     DevBuf d_data, d_off, d_out;
-    cc_status s = stage_messages(c, n, data, offsets, d_data, d_off);
+    cc_status s = stage_messages(n, data, offsets, d_data, d_off);
     if (s) return s;
     if (d_out.ensure(n * 48)) return CC_ERR_HIP;
-    KCK(cck_shake256_48(n, d_data.as<uint8_t>(), d_off.as<uint64_t>(), d_out.as<uint8_t>(), c->stream));
-    HIPCK(hipMemcpyAsync(out48, d_out.p, n * 48, hipMemcpyDeviceToHost, c->stream));
-    HIPCK(hipStreamSynchronize(c->stream));
-    return CC_OK;
+    HostForm f(c->stream);
+    f.up(d_data, data, offsets[n]);
+    f.up(d_off, offsets, (n + 1) * 8);
+    f.launch([&] {
+        return cck_shake256_48(n, d_data.as<uint8_t>(), d_off.as<uint64_t>(), d_out.as<uint8_t>(), c->stream);
+    });
+    f.down(out48, d_out, n * 48);
+    return f.finish();
 }
 
 // ---------------------------------------------------------------- issuance (§8(f) row 3)
@@ -1505,19 +1392,7 @@ static cc_status compute_h_batch(cc_ctx* c, size_t n, size_t q, size_t k, const 
         off[r] = r * len;
     }
     off[n] = n * len;
-    DevBuf d_data, d_off, d_fail;
-    cc_status s = stage_messages(c, n, data.data(), off.data(), d_data, d_off);
-    if (s) return s;
-    if (d_h.ensure(n * sb) || d_fail.ensure(4)) return CC_ERR_HIP;
-    HIPCK(hipMemsetAsync(d_fail.p, 0, 4, c->stream));
-    // the reference hashes commitment.to_bytes() and the known messages' to_bytes() (canonical)
-    KCK(cck_h_input_canon(sig_group(c->mode), n, len, (int)kn, d_data.as<uint8_t>(), c->stream));
-    KCK(cck_hash_to_curve(sig_group(c->mode), n, d_data.as<uint8_t>(), d_off.as<uint64_t>(), d_h.as<uint8_t>(),
-                          d_fail.as<uint32_t>(), c->stream));
-    uint32_t fail = 0;
-    HIPCK(hipMemcpyAsync(&fail, d_fail.p, 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCK(hipStreamSynchronize(c->stream));
-    return fail ? CC_ERR_DECODE : CC_OK;  // as cc_hash_to_curve
+    return hash_rows(c, sig_group(c->mode), n, data.data(), off.data(), len, (int)kn, d_h, nullptr);
 }
 
 cc_status cc_blind_sign_batch(cc_ctx* c, size_t n, size_t q, size_t k, const uint8_t* commitment, const uint8_t* known,
@@ -1544,18 +1419,28 @@ cc_status cc_blind_sign_batch(cc_ctx* c, size_t n, size_t q, size_t k, const uin
         return CC_ERR_HIP;
     s = agg_scratch(c, sg, 2 * n, t);
     if (s) return s;
-    if (k) HIPCK(hipMemcpyAsync(d_cts.p, ciphertexts, n * k * 2 * sb, hipMemcpyHostToDevice, st));
-    if (q > k) HIPCK(hipMemcpyAsync(d_known.p, known, n * (q - k) * 48, hipMemcpyHostToDevice, st));
-    HIPCK(hipMemcpyAsync(d_x.p, x, 48, hipMemcpyHostToDevice, st));
-    if (q) HIPCK(hipMemcpyAsync(d_y.p, y, q * 48, hipMemcpyHostToDevice, st));
-    KCK(cck_blind_assemble(sg, n, (int)q, (int)k, d_cts.as<uint8_t>(), d_h.as<uint8_t>(), d_known.as<uint8_t>(),
-                           d_x.as<uint8_t>(), d_y.as<uint8_t>(), d_pts.as<uint8_t>(), d_sc.as<uint32_t>(), st));
-    KCK(cck_msm_straus(sg, 2 * n, t, d_pts.as<uint8_t>(), t * sb, 0, sb, d_sc.as<uint32_t>(), 1,
-                       c->agg_scratch.as<uint32_t>(), d_out.as<uint8_t>(), st));
+    const size_t scr = 2 * n * cck_straus_words(sg, t) * 4;
     std::vector<uint8_t> o(2 * n * sb);
-    HIPCK(hipMemcpyAsync(o.data(), d_out.p, 2 * n * sb, hipMemcpyDeviceToHost, st));
-    HIPCK(hipMemcpyAsync(out_h, d_h.p, n * sb, hipMemcpyDeviceToHost, st));
-    HIPCK(hipStreamSynchronize(st));
+    HostForm f(st);
+    f.up(d_cts, ciphertexts, n * k * 2 * sb);
+    f.up(d_known, known, n * (q - k) * 48);
+    f.up_secret(d_x, x, 48);
+    f.up_secret(d_y, y, q * 48);
+    f.launch([&]() -> cc_status {
+        KCK(cck_blind_assemble(sg, n, (int)q, (int)k, d_cts.as<uint8_t>(), d_h.as<uint8_t>(), d_known.as<uint8_t>(),
+                               d_x.as<uint8_t>(), d_y.as<uint8_t>(), d_pts.as<uint8_t>(), d_sc.as<uint32_t>(), st));
+        KCK(cck_msm_straus(sg, 2 * n, t, d_pts.as<uint8_t>(), t * sb, 0, sb, d_sc.as<uint32_t>(), 1,
+                           c->agg_scratch.as<uint32_t>(), d_out.as<uint8_t>(), st));
+        return CC_OK;
+    });
+    f.down(o.data(), d_out, 2 * n * sb);
+    f.down(out_h, d_h, n * sb);
+    // the device copies of x and y, of the tasks' scalars (y_i, x + sum y m) and of their digits (the Straus
+    // scratch) are zeroed, as cc_blind_sign_batch_device zeroes its own
+    f.wipe(d_sc, 2 * n * t * 32);
+    f.wipe(c->agg_scratch, scr);
+    s = f.finish();
+    if (s) return s;
     for (size_t r = 0; r < n; r++) {
         memcpy(out_c1 + r * sb, &o[(2 * r) * sb], sb);
         memcpy(out_c2 + r * sb, &o[(2 * r + 1) * sb], sb);
@@ -1592,19 +1477,21 @@ cc_status cc_sigreq_verify_batch(cc_ctx* c, size_t n, size_t q, size_t k, const 
         d_pk.ensure(n * sb) || d_pr.ensure(n * pb) || d_ch.ensure(n * 48) ||
         d_scr.ensure(cck_sigreq_scratch_words(sg, n, (int)k) * 4) || d_ok.ensure(n * (2 + 2 * k)) || d_v.ensure(n))
         return CC_ERR_HIP;
-    HIPCK(hipMemcpyAsync(d_g.p, g, sb, hipMemcpyHostToDevice, st));
-    if (k) HIPCK(hipMemcpyAsync(d_hv.p, hvec, k * sb, hipMemcpyHostToDevice, st));
-    HIPCK(hipMemcpyAsync(d_comm.p, commitment, n * sb, hipMemcpyHostToDevice, st));
-    if (k) HIPCK(hipMemcpyAsync(d_cts.p, ciphertexts, n * k * 2 * sb, hipMemcpyHostToDevice, st));
-    HIPCK(hipMemcpyAsync(d_pk.p, elgamal_pk, n * sb, hipMemcpyHostToDevice, st));
-    HIPCK(hipMemcpyAsync(d_pr.p, proofs, n * pb, hipMemcpyHostToDevice, st));
-    HIPCK(hipMemcpyAsync(d_ch.p, chal, n * 48, hipMemcpyHostToDevice, st));
-    KCK(cck_sigreq_verify(sg, n, (int)k, d_g.as<uint8_t>(), d_hv.as<uint8_t>(), d_comm.as<uint8_t>(),
-                          d_cts.as<uint8_t>(), d_pk.as<uint8_t>(), d_pr.as<uint8_t>(), d_ch.as<uint8_t>(),
-                          d_h.as<uint8_t>(), d_scr.as<uint32_t>(), d_ok.as<uint8_t>(), d_v.as<uint8_t>(), st));
-    HIPCK(hipMemcpyAsync(verdicts, d_v.p, n, hipMemcpyDeviceToHost, st));
-    HIPCK(hipStreamSynchronize(st));
-    return CC_OK;
+    HostForm f(st);
+    f.up(d_g, g, sb);
+    f.up(d_hv, hvec, k * sb);
+    f.up(d_comm, commitment, n * sb);
+    f.up(d_cts, ciphertexts, n * k * 2 * sb);
+    f.up(d_pk, elgamal_pk, n * sb);
+    f.up(d_pr, proofs, n * pb);
+    f.up(d_ch, chal, n * 48);
+    f.launch([&] {
+        return cck_sigreq_verify(sg, n, (int)k, d_g.as<uint8_t>(), d_hv.as<uint8_t>(), d_comm.as<uint8_t>(),
+                                 d_cts.as<uint8_t>(), d_pk.as<uint8_t>(), d_pr.as<uint8_t>(), d_ch.as<uint8_t>(),
+                                 d_h.as<uint8_t>(), d_scr.as<uint32_t>(), d_ok.as<uint8_t>(), d_v.as<uint8_t>(), st);
+    });
+    f.down(verdicts, d_v, n);
+    return f.finish();
 }
 
 // ---------------------------------------------------------------- keygen: Pedersen VSS (§8(f) row 4)
@@ -1625,17 +1512,19 @@ cc_status cc_vss_verify_batch(cc_ctx* c, size_t n, size_t t, const uint8_t* g, c
     if (d_g.ensure(97) || d_h.ensure(97) || d_c.ensure(n_sets * t * 97) || d_set.ensure(n * 4) || d_ids.ensure(n * 8) ||
         d_sh.ensure(n * 96) || d_scr.ensure(n * (t + 2) * 33 * 4) || d_ok.ensure(n))
         return CC_ERR_HIP;
-    HIPCK(hipMemcpyAsync(d_g.p, g, 97, hipMemcpyHostToDevice, st));
-    HIPCK(hipMemcpyAsync(d_h.p, h, 97, hipMemcpyHostToDevice, st));
-    HIPCK(hipMemcpyAsync(d_c.p, commitments, n_sets * t * 97, hipMemcpyHostToDevice, st));
-    HIPCK(hipMemcpyAsync(d_set.p, set_of, n * 4, hipMemcpyHostToDevice, st));
-    HIPCK(hipMemcpyAsync(d_ids.p, ids, n * 8, hipMemcpyHostToDevice, st));
-    HIPCK(hipMemcpyAsync(d_sh.p, shares, n * 96, hipMemcpyHostToDevice, st));
-    KCK(cck_vss_verify(n, (int)t, d_g.as<uint8_t>(), d_h.as<uint8_t>(), d_c.as<uint8_t>(), d_set.as<uint32_t>(),
-                       d_ids.as<uint64_t>(), d_sh.as<uint8_t>(), d_scr.as<uint32_t>(), d_ok.as<uint8_t>(), st));
-    HIPCK(hipMemcpyAsync(verdicts, d_ok.p, n, hipMemcpyDeviceToHost, st));
-    HIPCK(hipStreamSynchronize(st));
-    return CC_OK;
+    HostForm f(st);
+    f.up(d_g, g, 97);
+    f.up(d_h, h, 97);
+    f.up(d_c, commitments, n_sets * t * 97);
+    f.up(d_set, set_of, n * 4);
+    f.up(d_ids, ids, n * 8);
+    f.up(d_sh, shares, n * 96);
+    f.launch([&] {
+        return cck_vss_verify(n, (int)t, d_g.as<uint8_t>(), d_h.as<uint8_t>(), d_c.as<uint8_t>(), d_set.as<uint32_t>(),
+                              d_ids.as<uint64_t>(), d_sh.as<uint8_t>(), d_scr.as<uint32_t>(), d_ok.as<uint8_t>(), st);
+    });
+    f.down(verdicts, d_ok, n);
+    return f.finish();
 }
 
 // ---------------------------------------------------------------- issuer table (config 4)
@@ -1674,32 +1563,13 @@ cc_status cc_set_issuers(cc_ctx* c, size_t n_iss, size_t q, const uint64_t* ids,
     }
     // the widest window whose tables fit the budget (16 GiB of the 288 GB HBM, at most half of what is
     // free; cc_set_table_bits forces a width): t x nwin additions per aggregated key, nwin = ceil(256 / w).
-    // The old table is released first so its memory counts as free (identical calls pick the same width).
     c->iss_table.release();
-    const double budget = std::min(16.0 * (double)(1ull << 30), 0.5 * (double)free_hbm());
-    int wb = 8;
-    if (c->force_iss_bits >= 8 && c->force_iss_bits <= 16) {
-        wb = c->force_iss_bits;
-    } else {
-        for (int cand : {16, 13, 12, 10})
-            if ((double)(nb * tab_words(og, cand) * 4) <= budget) {
-                wb = cand;
-                break;
-            }
-    }
+    auto tbytes = [&](int w) { return nb * tab_words(og, w) * 4; };
+    int wb = pick_table_bits(c->force_iss_bits, 16.0 * (double)(1ull << 30), tbytes);
     if (c->iss_ids.ensure(n_iss * 8) || c->iss_aff.ensure(nb * aw * 4) || c->iss_inf.ensure(nb * 4))
         return CC_ERR_HIP;
-    const double fr = (double)free_hbm();
-    if (fr > 0 && (double)(nb * tab_words(og, wb) * 4) > 0.9 * fr) {  // see rebuild_tables
-        if (c->force_iss_bits) return CC_ERR_HIP;
-        wb = 8;
-    }
-    if (c->iss_table.ensure(nb * tab_words(og, wb) * 4)) {
-        (void)hipGetLastError();  // clear the failed allocation's error
-        if (c->force_iss_bits) return CC_ERR_HIP;
-        wb = 8;                   // the wide table did not fit the free HBM
-        if (c->iss_table.ensure(nb * tab_words(og, wb) * 4)) return CC_ERR_HIP;
-    }
+    wb = alloc_tables(wb, c->force_iss_bits != 0, tbytes, [&](int w) { return c->iss_table.ensure(tbytes(w)) == 0; });
+    if (!wb) return CC_ERR_HIP;
     cc_status s = decode_points_host(c, og, nb, enc.data(), c->iss_aff.as<uint32_t>(), c->iss_inf.as<uint32_t>());
     if (s) return s;
     HIPCK(hipMemcpy(c->iss_ids.p, sid.data(), n_iss * 8, hipMemcpyHostToDevice));
@@ -1708,7 +1578,6 @@ cc_status cc_set_issuers(cc_ctx* c, size_t n_iss, size_t q, const uint64_t* ids,
     KCK(cck_build_table(og, (int)nb, wb, c->iss_aff.as<uint32_t>(), c->iss_inf.as<uint32_t>(), pw.as<uint32_t>(),
                         c->iss_table.as<uint32_t>(), 1, c->stream));
     HIPCK(hipStreamSynchronize(c->stream));
-    pw.release();
     c->iss_n = n_iss;
     c->iss_q = q;
     c->iss_wbits = wb;
@@ -1741,9 +1610,7 @@ cc_status cc_verkey_aggregate_ids_device(cc_ctx* c, size_t n, size_t len, size_t
     c = primary(c);  // a device set forwards to its first device
     if (!c || (n && (!d_ids || !d_outX || (c->iss_q && !d_outY)))) return CC_ERR_DECODE;
     if (!c->iss_n) return CC_ERR_STATE;
-    if (len > kMaxIds) return CC_ERR_DECODE;
-    if (len < t || len == 0) return CC_ERR_THRESHOLD;
-    if (n > kMaxBatch) return CC_ERR_DECODE;
+    if (cc_status e = agg_checks(n, len, t)) return e;
     if (!n) return CC_OK;
     HIPCK(hipSetDevice(c->device));
     hipStream_t st = stream ? (hipStream_t)stream : c->stream;
@@ -1764,9 +1631,7 @@ cc_status cc_aggregate_credential_batch_device(cc_ctx* c, size_t n, size_t len, 
     if (!c || (n && (!d_ids || !d_s1 || !d_s2 || !d_out_s1 || !d_out_s2 || !d_outX || (c->iss_q && !d_outY))))
         return CC_ERR_DECODE;
     if (!c->iss_n) return CC_ERR_STATE;
-    if (len > kMaxIds) return CC_ERR_DECODE;
-    if (len < t || len == 0) return CC_ERR_THRESHOLD;
-    if (n > kMaxBatch) return CC_ERR_DECODE;
+    if (cc_status e = agg_checks(n, len, t)) return e;
     if (!n) return CC_OK;
     HIPCK(hipSetDevice(c->device));
     hipStream_t st = stream ? (hipStream_t)stream : c->stream;
@@ -1814,9 +1679,7 @@ cc_status cc_verkey_aggregate_ids(cc_ctx* c, size_t n, size_t len, size_t t, con
     c = primary(c);  // a device set forwards to its first device
     if (!c || (n && (!ids || !outX || (c->iss_q && !outY)))) return CC_ERR_DECODE;
     if (!c->iss_n) return CC_ERR_STATE;
-    if (len > kMaxIds) return CC_ERR_DECODE;
-    if (len < t || len == 0) return CC_ERR_THRESHOLD;
-    if (n > kMaxBatch) return CC_ERR_DECODE;
+    if (cc_status e = agg_checks(n, len, t)) return e;
     if (!n) return CC_OK;
     for (size_t i = 0; i < n; i++)
         for (size_t k = 0; k < t; k++)
@@ -1866,6 +1729,23 @@ static cc_status check_revealed(size_t q, size_t r, const uint64_t* rev_idx, std
     return CC_OK;
 }
 
+// the checks of the PoK forms after the NULL checks, in the header's order; with_vk: verify and
+// PoKOfSignature::init need the verkey's tables, gen_proof only the shape
+static cc_status prove_checks(const cc_ctx* c, bool with_vk, size_t q, size_t r, size_t nresp, const uint64_t* rev_idx,
+                              std::vector<uint32_t>& idx) {
+    if (with_vk) {
+        if (!c->have_params || !c->have_vk) return CC_ERR_STATE;
+        if (q != c->q) return CC_ERR_LEN;
+    } else if (q > kMaxQ) {
+        return CC_ERR_DECODE;
+    }
+    // more than q indices hold one >= q or a repeated one among the first q + 1
+    cc_status s = check_revealed(q, std::min(r, q + 1), rev_idx, idx);
+    if (s) return s;
+    if (nresp != q - r + 1) return CC_ERR_BASES_EXPS;
+    return CC_OK;
+}
+
 static cc_status launch_pok(cc_ctx* c, const VerifyWork& w, size_t n, size_t q, size_t r, const uint8_t* d_s1,
                             const uint8_t* d_s2, const uint8_t* d_J, const uint8_t* d_T, const uint8_t* d_resp,
                             const uint8_t* d_chal, const uint32_t* d_idx, const uint8_t* d_rev_msgs, uint8_t* d_verdicts,
@@ -1876,14 +1756,7 @@ static cc_status launch_pok(cc_ctx* c, const VerifyWork& w, size_t n, size_t q, 
         c->mode, n, (int)q, (int)r, d_s1, d_s2, d_J, d_T, d_resp, d_chal, d_rev_msgs, d_idx, c->vk_aff.as<uint32_t>(),
         c->X_inf, c->table.as<uint32_t>(), c->wbits, c->table_inf.as<uint32_t>(), w.prep->as<uint32_t>(),
         w.flags->as<uint32_t>(), w.scratch->as<uint32_t>(), st));  // J*chal window table: the fexp scratch, free until fexp
-    if (c->timing) (void)hipEventRecord(c->ev[1], st);
-    cc_status ms = launch_miller(c, w, n, st);
-    if (ms) return ms;
-    if (c->timing) (void)hipEventRecord(c->ev[2], st);
-    KCK(cck_fexp(n, w.fbuf->as<uint32_t>(), w.scratch->as<uint32_t>(), w.flags->as<uint32_t>(), d_verdicts, d_gt,
-                 kFexpWideMax, st));
-    if (c->timing) (void)hipEventRecord(c->ev[3], st);
-    return CC_OK;
+    return launch_pairings(c, w, n, d_verdicts, d_gt, st);
 }
 
 cc_status cc_pok_verify_batch_device(cc_ctx* c, size_t n, size_t q, size_t r, size_t nresp, const uint8_t* d_s1,
@@ -1894,27 +1767,20 @@ cc_status cc_pok_verify_batch_device(cc_ctx* c, size_t n, size_t q, size_t r, si
     if (!c || (n && (!d_s1 || !d_s2 || !d_J || !d_T || !d_chal || !d_verdicts || (nresp && !d_resp) ||
                      (r && (!rev_idx || !d_rev_msgs)))))
         return CC_ERR_DECODE;
-    if (!c->have_params || !c->have_vk) return CC_ERR_STATE;
-    if (q != c->q) return CC_ERR_LEN;
     std::vector<uint32_t> idx;
-    cc_status s = check_revealed(q, r, rev_idx, idx);
+    cc_status s = prove_checks(c, true, q, r, nresp, rev_idx, idx);
     if (s) return s;
-    if (nresp != q - r + 1) return CC_ERR_BASES_EXPS;
     if (n > kMaxBatch) return CC_ERR_DECODE;
     if (!n) return CC_OK;
     HIPCK(hipSetDevice(c->device));
     hipStream_t st = stream ? (hipStream_t)stream : c->stream;
     if (c->concurrency > 1) {  // the next concurrency slot (cc_set_concurrency): its own tables of d J
-        int k = 0;
-        VerifyWork w;
-        s = slot_begin(c, st, cc::slots::verify_sizes(n, 0, (n * 15 * 84 + 72 * 12) * 4, idx.size() * 4 + 4), k, w);
-        if (s) return s;
-        SlotFence fence(c->pool, c->dev, k, st);
-        if (r) KCK(c->stage[(size_t)k].upload(w.idx->p, idx.data(), idx.size() * 4, st));  // pinned ring
-        s = launch_pok(c, w, n, q, r, d_s1, d_s2, d_J, d_T, d_resp, d_chal, w.idx->as<uint32_t>(), d_rev_msgs,
-                       d_verdicts, d_gt, st);
-        if (s) return s;
-        return fence.close() ? CC_ERR_HIP : CC_OK;
+        const cc::slots::Sizes sz = cc::slots::verify_sizes(n, 0, (n * 15 * 84 + 72 * 12) * 4, idx.size() * 4 + 4);
+        return on_slot(c, st, sz, [&](int k, const VerifyWork& w) -> cc_status {
+            if (r) KCK(c->stage[(size_t)k].upload(w.idx->p, idx.data(), idx.size() * 4, st));  // pinned ring
+            return launch_pok(c, w, n, q, r, d_s1, d_s2, d_J, d_T, d_resp, d_chal, w.idx->as<uint32_t>(), d_rev_msgs,
+                              d_verdicts, d_gt, st);
+        });
     }
     s = ensure_work(c, n);
     if (s) return s;
@@ -1939,12 +1805,9 @@ cc_status cc_pok_rlc_partial_device(cc_ctx* c, size_t n, size_t q, size_t r, siz
     if (!c || !seed32 || !d_partial ||
         (n && (!d_s1 || !d_s2 || !d_J || !d_T || !d_chal || (nresp && !d_resp) || (r && (!rev_idx || !d_rev_msgs)))))
         return CC_ERR_DECODE;
-    if (!c->have_params || !c->have_vk) return CC_ERR_STATE;
-    if (q != c->q) return CC_ERR_LEN;
     std::vector<uint32_t> idx;
-    cc_status s = check_revealed(q, r, rev_idx, idx);
+    cc_status s = prove_checks(c, true, q, r, nresp, rev_idx, idx);
     if (s) return s;
-    if (nresp != q - r + 1) return CC_ERR_BASES_EXPS;
     if (n > kMaxBatch) return CC_ERR_DECODE;
     HIPCK(hipSetDevice(c->device));
     hipStream_t st = stream ? (hipStream_t)stream : c->stream;
@@ -1952,22 +1815,15 @@ cc_status cc_pok_rlc_partial_device(cc_ctx* c, size_t n, size_t q, size_t r, siz
     const size_t jtab_b = (n * 15 * 84 + 72 * 12) * 4;  // the tables of d J (ensure_work)
     PokRlcArgs pok{r, d_J, d_T, d_resp, d_chal, d_rev_msgs, nullptr, pok_rlc_twin(c, n)};
     if (c->concurrency > 1) {  // the next concurrency slot (cc_set_concurrency): its own workspaces
-        int k = 0;
-        VerifyWork w;
-        s = slot_begin(c, st, cc::slots::verify_sizes(n, 0, jtab_b, idx.size() * 4 + 4), k, w);
-        if (s) return s;
-        SlotFence fence(c->pool, c->dev, k, st);
-        VerifySlot* sl = k ? c->vslots[(size_t)k - 1] : nullptr;
-        RlcWork rw = sl ? RlcWork{&sl->prep, &sl->flags, &sl->fbuf, &sl->scratch, &sl->rkey, &sl->rany, &sl->rpts,
-                                  &sl->rdig, &sl->rwork}
-                        : ctx_rlc_work(c);
-        if (rlc_ensure(c, rw, n, &c->pool.recs[(size_t)k], jtab_b, pok.twin)) return CC_ERR_HIP;
-        if (r) KCK(c->stage[(size_t)k].upload(w.idx->p, idx.data(), idx.size() * 4, st));  // pinned ring
-        pok.d_idx = w.idx->as<uint32_t>();
-        s = launch_rlc_partial(c, rw, n, q, base_index, seed32, d_s1, d_s2, nullptr, d_partial, st,
-                               &c->stage[(size_t)k], &pok);
-        if (s) return s;
-        return fence.close() ? CC_ERR_HIP : CC_OK;
+        const cc::slots::Sizes sz = cc::slots::verify_sizes(n, 0, jtab_b, idx.size() * 4 + 4);
+        return on_slot(c, st, sz, [&](int k, const VerifyWork& w) -> cc_status {
+            RlcWork rw = slot_rlc_work(c, k);
+            if (rlc_ensure(c, rw, n, &c->pool.recs[(size_t)k], jtab_b, pok.twin)) return CC_ERR_HIP;
+            if (r) KCK(c->stage[(size_t)k].upload(w.idx->p, idx.data(), idx.size() * 4, st));  // pinned ring
+            pok.d_idx = w.idx->as<uint32_t>();
+            return launch_rlc_partial(c, rw, n, q, base_index, seed32, d_s1, d_s2, nullptr, d_partial, st,
+                                      &c->stage[(size_t)k], &pok);
+        });
     }
     drain_slots(c);  // concurrent batches (cc_set_concurrency) may still use the buffers sized below
     s = ensure_work(c, n);
@@ -1988,12 +1844,9 @@ static cc_status pok_host(cc_ctx* c, size_t n, size_t q, size_t r, size_t nresp,
     c = primary(c);  // a device set forwards to its first device
     if (!c || (n && (!s1 || !s2 || !J || !T || !chal || !verdicts || (nresp && !resp) || (r && (!rev_idx || !rev_msgs)))))
         return CC_ERR_DECODE;
-    if (!c->have_params || !c->have_vk) return CC_ERR_STATE;
-    if (q != c->q) return CC_ERR_LEN;
     std::vector<uint32_t> idx;
-    cc_status s = check_revealed(q, r, rev_idx, idx);
+    cc_status s = prove_checks(c, true, q, r, nresp, rev_idx, idx);
     if (s) return s;
-    if (nresp != q - r + 1) return CC_ERR_BASES_EXPS;
     if (n > kMaxBatch) return CC_ERR_DECODE;
     if (!n) return CC_OK;
     HIPCK(hipSetDevice(c->device));
@@ -2077,14 +1930,7 @@ static cc_status launch_pok_pervk(cc_ctx* c, const VerifyWork& w, size_t n, size
     KCK(cck_prep_pok_var(c->mode, n, (int)q, (int)r, d_s1, d_s2, d_J, d_T, d_resp, d_chal, d_rev_msgs, d_idx, d_vkX,
                          d_vkY, c->gtilde_aff.as<uint32_t>(), c->gtilde_inf, w.vkb->as<uint32_t>(),
                          w.prep->as<uint32_t>(), w.flags->as<uint32_t>(), st));
-    if (c->timing) (void)hipEventRecord(c->ev[1], st);
-    cc_status ms = launch_miller(c, w, n, st);
-    if (ms) return ms;
-    if (c->timing) (void)hipEventRecord(c->ev[2], st);
-    KCK(cck_fexp(n, w.fbuf->as<uint32_t>(), w.scratch->as<uint32_t>(), w.flags->as<uint32_t>(), d_verdicts, d_gt,
-                 kFexpWideMax, st));
-    if (c->timing) (void)hipEventRecord(c->ev[3], st);
-    return CC_OK;
+    return launch_pairings(c, w, n, d_verdicts, d_gt, st);
 }
 
 // the checks of cc_pok_verify_batch_device in its order, without a loaded verkey (q <= the pervk ceiling)
@@ -2120,16 +1966,12 @@ cc_status cc_pok_verify_batch_pervk_device(cc_ctx* c, size_t n, size_t q, size_t
     hipStream_t st = stream ? (hipStream_t)stream : c->stream;
     const size_t vkw = cck_prep_pok_var_words(c->mode, n, q) * 4;
     if (c->concurrency > 1) {  // the next concurrency slot (cc_set_concurrency): its own tables and indices
-        int k = 0;
-        VerifyWork w;
-        s = slot_begin(c, st, cc::slots::verify_sizes(n, vkw, 0, idx.size() * 4 + 4), k, w);
-        if (s) return s;
-        SlotFence fence(c->pool, c->dev, k, st);
-        if (r) KCK(c->stage[(size_t)k].upload(w.idx->p, idx.data(), idx.size() * 4, st));  // pinned ring
-        s = launch_pok_pervk(c, w, n, q, r, d_s1, d_s2, d_J, d_T, d_resp, d_chal, w.idx->as<uint32_t>(), d_rev_msgs,
-                             d_vkX, d_vkY, d_verdicts, d_gt, st);
-        if (s) return s;
-        return fence.close() ? CC_ERR_HIP : CC_OK;
+        const cc::slots::Sizes sz = cc::slots::verify_sizes(n, vkw, 0, idx.size() * 4 + 4);
+        return on_slot(c, st, sz, [&](int k, const VerifyWork& w) -> cc_status {
+            if (r) KCK(c->stage[(size_t)k].upload(w.idx->p, idx.data(), idx.size() * 4, st));  // pinned ring
+            return launch_pok_pervk(c, w, n, q, r, d_s1, d_s2, d_J, d_T, d_resp, d_chal, w.idx->as<uint32_t>(),
+                                    d_rev_msgs, d_vkX, d_vkY, d_verdicts, d_gt, st);
+        });
     }
     s = ensure_work(c, n);
     if (s) return s;
@@ -2189,23 +2031,6 @@ cc_status cc_pok_verify_batch_pervk(cc_ctx* c, size_t n, size_t q, size_t r, siz
 
 
 // ---------------------------------------------------------------- holder side (pok_prove.hip)
-// the checks cc_pok_verify_batch_device makes, in its order; with_vk: PoKOfSignature::init needs the
-// verkey's tables, gen_proof only the shape
-static cc_status prove_checks(const cc_ctx* c, bool with_vk, size_t q, size_t r, size_t nresp, const uint64_t* rev_idx,
-                              std::vector<uint32_t>& idx) {
-    if (with_vk) {
-        if (!c->have_params || !c->have_vk) return CC_ERR_STATE;
-        if (q != c->q) return CC_ERR_LEN;
-    } else if (q > kMaxQ) {
-        return CC_ERR_DECODE;
-    }
-    // more than q indices hold one >= q or a repeated one among the first q + 1
-    cc_status s = check_revealed(q, std::min(r, q + 1), rev_idx, idx);
-    if (s) return s;
-    if (nresp != q - r + 1) return CC_ERR_BASES_EXPS;
-    return CC_OK;
-}
-
 static cc_status launch_pok_init(cc_ctx* c, size_t n, size_t q, size_t r, const uint8_t* d_s1, const uint8_t* d_s2,
                                  const uint8_t* d_msgs, const uint32_t* d_idx, const uint8_t* d_rand, uint8_t* d_o1,
                                  uint8_t* d_o2, uint8_t* d_J, uint8_t* d_T, hipStream_t st) {
@@ -2261,28 +2086,24 @@ cc_status cc_pok_init_batch(cc_ctx* c, size_t n, size_t q, size_t r, size_t nres
         d1.ensure(n * sb) || d2.ensure(n * sb) || dJ.ensure(n * ob) || dT.ensure(n * ob) ||
         c->prove_idx.ensure(idx.size() * 4) || c->prove_scratch.ensure(scr))
         return CC_ERR_HIP;
-    auto run = [&]() -> cc_status {
-        HIPCK(hipMemcpyAsync(c->in_s1.p, s1, n * sb, hipMemcpyHostToDevice, st));
-        HIPCK(hipMemcpyAsync(c->in_s2.p, s2, n * sb, hipMemcpyHostToDevice, st));
-        if (q) HIPCK(hipMemcpyAsync(c->in_msgs.p, msgs, n * q * 48, hipMemcpyHostToDevice, st));
-        HIPCK(hipMemcpyAsync(dR.p, rand, rb, hipMemcpyHostToDevice, st));
-        HIPCK(hipMemcpyAsync(c->prove_idx.p, idx.data(), idx.size() * 4, hipMemcpyHostToDevice, st));
-        cc_status e = launch_pok_init(c, n, q, r, c->in_s1.as<uint8_t>(), c->in_s2.as<uint8_t>(), c->in_msgs.as<uint8_t>(),
-                                      c->prove_idx.as<uint32_t>(), dR.as<uint8_t>(), d1.as<uint8_t>(), d2.as<uint8_t>(),
-                                      dJ.as<uint8_t>(), dT.as<uint8_t>(), st);
-        if (e) return e;
-        HIPCK(hipMemcpyAsync(o1, d1.p, n * sb, hipMemcpyDeviceToHost, st));
-        HIPCK(hipMemcpyAsync(o2, d2.p, n * sb, hipMemcpyDeviceToHost, st));
-        HIPCK(hipMemcpyAsync(oJ, dJ.p, n * ob, hipMemcpyDeviceToHost, st));
-        HIPCK(hipMemcpyAsync(oT, dT.p, n * ob, hipMemcpyDeviceToHost, st));
-        return CC_OK;
-    };
-    s = run();
+    HostForm f(st);
+    f.up(c->in_s1, s1, n * sb);
+    f.up(c->in_s2, s2, n * sb);
+    f.up(c->in_msgs, msgs, n * q * 48);
+    f.up_secret(dR, rand, rb);
+    f.up(c->prove_idx, idx.data(), idx.size() * 4);
+    f.launch([&] {
+        return launch_pok_init(c, n, q, r, c->in_s1.as<uint8_t>(), c->in_s2.as<uint8_t>(), c->in_msgs.as<uint8_t>(),
+                               c->prove_idx.as<uint32_t>(), dR.as<uint8_t>(), d1.as<uint8_t>(), d2.as<uint8_t>(),
+                               dJ.as<uint8_t>(), dT.as<uint8_t>(), st);
+    });
+    f.down(o1, d1, n * sb);
+    f.down(o2, d2, n * sb);
+    f.down(oJ, dJ, n * ob);
+    f.down(oT, dT, n * ob);
     // the device copies of the secrets (r1, r2, the blindings; the digits of r1 and r1 r2) are zeroed
-    const bool wiped = hipMemsetAsync(dR.p, 0, rb, st) == hipSuccess &&
-                       hipMemsetAsync(c->prove_scratch.p, 0, scr, st) == hipSuccess;
-    if (hipStreamSynchronize(st) != hipSuccess || !wiped) return s ? s : CC_ERR_HIP;
-    return s;
+    f.wipe(c->prove_scratch, scr);
+    return f.finish();
 }
 
 cc_status cc_pok_gen_proof_batch_device(cc_ctx* c, size_t n, size_t q, size_t r, size_t nresp, const uint8_t* d_msgs,
@@ -2323,20 +2144,17 @@ cc_status cc_pok_gen_proof_batch(cc_ctx* c, size_t n, size_t q, size_t r, size_t
     if (c->in_msgs.ensure(n * q * 48 + 16) || dR.ensure(rb) || dC.ensure(n * 48) || dO.ensure(n * nresp * 48) ||
         c->prove_idx.ensure(idx.size() * 4))
         return CC_ERR_HIP;
-    auto run = [&]() -> cc_status {
-        if (q) HIPCK(hipMemcpyAsync(c->in_msgs.p, msgs, n * q * 48, hipMemcpyHostToDevice, st));
-        HIPCK(hipMemcpyAsync(dR.p, rand, rb, hipMemcpyHostToDevice, st));
-        HIPCK(hipMemcpyAsync(dC.p, chal, n * 48, hipMemcpyHostToDevice, st));
-        HIPCK(hipMemcpyAsync(c->prove_idx.p, idx.data(), idx.size() * 4, hipMemcpyHostToDevice, st));
-        KCK(cck_pok_responses(n, (int)q, (int)r, c->in_msgs.as<uint8_t>(), dR.as<uint8_t>(), dC.as<uint8_t>(),
-                              c->prove_idx.as<uint32_t>(), dO.as<uint8_t>(), st));
-        HIPCK(hipMemcpyAsync(out, dO.p, n * nresp * 48, hipMemcpyDeviceToHost, st));
-        return CC_OK;
-    };
-    s = run();
-    const bool wiped = hipMemsetAsync(dR.p, 0, rb, st) == hipSuccess;  // r2 and the blindings
-    if (hipStreamSynchronize(st) != hipSuccess || !wiped) return s ? s : CC_ERR_HIP;
-    return s;
+    HostForm f(st);
+    f.up(c->in_msgs, msgs, n * q * 48);
+    f.up_secret(dR, rand, rb);  // r2 and the blindings
+    f.up(dC, chal, n * 48);
+    f.up(c->prove_idx, idx.data(), idx.size() * 4);
+    f.launch([&] {
+        return cck_pok_responses(n, (int)q, (int)r, c->in_msgs.as<uint8_t>(), dR.as<uint8_t>(), dC.as<uint8_t>(),
+                                 c->prove_idx.as<uint32_t>(), dO.as<uint8_t>(), st);
+    });
+    f.down(out, dO, n * nresp * 48);
+    return f.finish();
 }
 
 cc_status cc_unblind_batch(cc_ctx* c, size_t n, const uint8_t* c1, const uint8_t* c2, const uint8_t* sk,
@@ -2358,27 +2176,24 @@ cc_status cc_unblind_batch(cc_ctx* c, size_t n, const uint8_t* c1, const uint8_t
     if (c->in_s1.ensure(n * sb) || c->in_s2.ensure(n * sb) || dK.ensure(n * 48) || dP.ensure(n * 2 * sb) ||
         dS.ensure(n * 64) || dO.ensure(n * sb))
         return CC_ERR_HIP;
-    cc_status s = agg_scratch(c, sg, n, 2);
-    if (s) return s;
-    auto run = [&]() -> cc_status {
-        HIPCK(hipMemcpyAsync(c->in_s1.p, c1, n * sb, hipMemcpyHostToDevice, st));
-        HIPCK(hipMemcpyAsync(c->in_s2.p, c2, n * sb, hipMemcpyHostToDevice, st));
-        HIPCK(hipMemcpyAsync(dK.p, sk, n * 48, hipMemcpyHostToDevice, st));
+    if (cc_status s = agg_scratch(c, sg, n, 2)) return s;
+    HostForm f(st);
+    f.up(c->in_s1, c1, n * sb);
+    f.up(c->in_s2, c2, n * sb);
+    f.up_secret(dK, sk, n * 48);
+    f.launch([&]() -> cc_status {
         KCK(cck_unblind_assemble(sg, n, c->in_s1.as<uint8_t>(), c->in_s2.as<uint8_t>(), dK.as<uint8_t>(),
                                  dP.as<uint8_t>(), dS.as<uint32_t>(), st));
         // sigma_2 = c2 + (-sk) c1: one t = 2 Straus task a row (as cc_blind_sign_batch drives it)
         KCK(cck_msm_straus(sg, n, 2, dP.as<uint8_t>(), 2 * sb, 0, sb, dS.as<uint32_t>(), 1,
                            c->agg_scratch.as<uint32_t>(), dO.as<uint8_t>(), st));
-        HIPCK(hipMemcpyAsync(out_sigma2, dO.p, n * sb, hipMemcpyDeviceToHost, st));
         return CC_OK;
-    };
-    s = run();
+    });
+    f.down(out_sigma2, dO, n * sb);
     // the device copies of sk, of -sk and of its digits (the Straus scratch) are zeroed
-    const bool wiped = hipMemsetAsync(dK.p, 0, n * 48, st) == hipSuccess &&
-                       hipMemsetAsync(dS.p, 0, n * 64, st) == hipSuccess &&
-                       hipMemsetAsync(c->agg_scratch.p, 0, scr, st) == hipSuccess;
-    if (hipStreamSynchronize(st) != hipSuccess || !wiped) return s ? s : CC_ERR_HIP;
-    return s;
+    f.wipe(dS, n * 64);
+    f.wipe(c->agg_scratch, scr);
+    return f.finish();
 }
 
 // ---------------------------------------------------------------- holder side of issuance (sigreq_prove.hip)
@@ -2401,31 +2216,12 @@ cc_status cc_set_request_params(cc_ctx* c, size_t q, const uint8_t* g, const uin
     std::vector<uint8_t> enc(nb * sb);  // [h_0 .. h_{q-1}, g]: g is table base q
     memcpy(enc.data(), h, q * sb);
     memcpy(enc.data() + q * sb, g, sb);
-    // the old table is released first so its memory counts as free (identical calls pick the same width)
     c->rq_table.release();
-    const double budget = std::min(kRqTableBudget, 0.5 * (double)free_hbm());
-    int wb = 8;
-    if (table_bits) {
-        wb = table_bits;
-    } else {
-        for (int cand : {16, 13, 12, 10})
-            if ((double)(nb * tab_words(sg, cand) * 4) <= budget) {
-                wb = cand;
-                break;
-            }
-    }
+    auto tbytes = [&](int w) { return nb * tab_words(sg, w) * 4; };
+    int wb = pick_table_bits(table_bits, kRqTableBudget, tbytes);
     if (c->rq_aff.ensure(nb * aw * 4) || c->rq_inf.ensure(nb * 4)) return CC_ERR_HIP;
-    const double fr = (double)free_hbm();
-    if (fr > 0 && (double)(nb * tab_words(sg, wb) * 4) > 0.9 * fr) {  // see rebuild_tables
-        if (table_bits || wb == 8) return CC_ERR_HIP;
-        wb = 8;
-    }
-    if (c->rq_table.ensure(nb * tab_words(sg, wb) * 4)) {
-        (void)hipGetLastError();  // clear the failed allocation's error
-        if (table_bits || wb == 8) return CC_ERR_HIP;
-        wb = 8;                   // the wide table did not fit the free HBM
-        if (c->rq_table.ensure(nb * tab_words(sg, wb) * 4)) return CC_ERR_HIP;
-    }
+    wb = alloc_tables(wb, table_bits != 0, tbytes, [&](int w) { return c->rq_table.ensure(tbytes(w)) == 0; });
+    if (!wb) return CC_ERR_HIP;
     cc_status s = decode_points_host(c, sg, nb, enc.data(), c->rq_aff.as<uint32_t>(), c->rq_inf.as<uint32_t>());
     if (s) return s;
     DevBuf pw;
@@ -2434,7 +2230,6 @@ cc_status cc_set_request_params(cc_ctx* c, size_t q, const uint8_t* g, const uin
     KCK(cck_build_table(sg, (int)nb, wb, c->rq_aff.as<uint32_t>(), c->rq_inf.as<uint32_t>(), pw.as<uint32_t>(),
                         c->rq_table.as<uint32_t>(), 1, c->stream));
     HIPCK(hipStreamSynchronize(c->stream));
-    pw.release();
     c->rq_q = q;
     c->rq_wbits = wb;
     c->have_rq = true;
@@ -2517,27 +2312,24 @@ cc_status cc_sigreq_new_batch(cc_ctx* c, size_t n, size_t q, size_t k, const uin
     if (c->in_msgs.ensure(mb + 16) || dR.ensure(rb) || dP.ensure(n * sb) || dC.ensure(n * sb) || dH.ensure(n * sb) ||
         dT.ensure(n * k * 2 * sb + 16))
         return CC_ERR_HIP;
-    s = rq_ensure_two(c, n, k);  // before run(): the wipe below covers the digits of this call
+    s = rq_ensure_two(c, n, k);  // before the launch: the wipe covers the digits of this call
     if (s) return s;
     uint32_t fail = 0;
-    auto run = [&]() -> cc_status {
-        HIPCK(hipMemcpyAsync(c->in_msgs.p, msgs, mb, hipMemcpyHostToDevice, st));
-        HIPCK(hipMemcpyAsync(dR.p, rand, rb, hipMemcpyHostToDevice, st));
-        if (k) HIPCK(hipMemcpyAsync(dP.p, pk, n * sb, hipMemcpyHostToDevice, st));
-        cc_status e = launch_sigreq_new(c, n, q, k, c->in_msgs.as<uint8_t>(), dP.as<uint8_t>(), dR.as<uint8_t>(),
-                                        dC.as<uint8_t>(), dH.as<uint8_t>(), dT.as<uint8_t>(), st);
-        if (e) return e;
-        HIPCK(hipMemcpyAsync(out_comm, dC.p, n * sb, hipMemcpyDeviceToHost, st));
-        HIPCK(hipMemcpyAsync(out_h, dH.p, n * sb, hipMemcpyDeviceToHost, st));
-        if (k) HIPCK(hipMemcpyAsync(out_cts, dT.p, n * k * 2 * sb, hipMemcpyDeviceToHost, st));
-        HIPCK(hipMemcpyAsync(&fail, c->rq_fail.p, 4, hipMemcpyDeviceToHost, st));
-        return CC_OK;
-    };
-    s = run();
+    HostForm f(st);
+    f.up_secret(c->in_msgs, msgs, mb);
+    f.up_secret(dR, rand, rb);
+    f.up(dP, pk, k ? n * sb : 0);
+    f.launch([&] {
+        return launch_sigreq_new(c, n, q, k, c->in_msgs.as<uint8_t>(), dP.as<uint8_t>(), dR.as<uint8_t>(),
+                                 dC.as<uint8_t>(), dH.as<uint8_t>(), dT.as<uint8_t>(), st);
+    });
+    f.down(out_comm, dC, n * sb);
+    f.down(out_h, dH, n * sb);
+    f.down(out_cts, dT, n * k * 2 * sb);
+    f.down(&fail, c->rq_fail, 4);
     // the device copies of the secrets (the messages, r and the k_i, the digits of k_i and m_i) are zeroed
-    bool wiped = hipMemsetAsync(c->in_msgs.p, 0, mb, st) == hipSuccess && hipMemsetAsync(dR.p, 0, rb, st) == hipSuccess;
-    if (k) wiped = hipMemsetAsync(c->rq_dig.p, 0, cck_rq_digit_bytes(n, (int)k), st) == hipSuccess && wiped;
-    if (hipStreamSynchronize(st) != hipSuccess || !wiped) return s ? s : CC_ERR_HIP;
+    f.wipe(c->rq_dig, k ? cck_rq_digit_bytes(n, (int)k) : 0);
+    s = f.finish();
     if (!s && fail) return CC_ERR_DECODE;  // as cc_hash_to_curve: 4,096 failed tries
     return s;
 }
@@ -2588,24 +2380,17 @@ cc_status cc_sigreq_pok_init_batch(cc_ctx* c, size_t n, size_t q, size_t k, cons
     if (dB.ensure(bb) || dP.ensure(n * sb) || dH.ensure(n * sb) || dO.ensure(pb)) return CC_ERR_HIP;
     s = rq_ensure_two(c, n, k);
     if (s) return s;
-    auto run = [&]() -> cc_status {
-        HIPCK(hipMemcpyAsync(dB.p, blind, bb, hipMemcpyHostToDevice, st));
-        if (k) {
-            HIPCK(hipMemcpyAsync(dP.p, pk, n * sb, hipMemcpyHostToDevice, st));
-            HIPCK(hipMemcpyAsync(dH.p, h, n * sb, hipMemcpyHostToDevice, st));
-        }
-        cc_status e = launch_sigreq_init(c, n, q, k, dH.as<uint8_t>(), dP.as<uint8_t>(), dB.as<uint8_t>(),
-                                         dO.as<uint8_t>(), st);
-        if (e) return e;
-        HIPCK(hipMemcpyAsync(out_proofs, dO.p, pb, hipMemcpyDeviceToHost, st));
-        return CC_OK;
-    };
-    s = run();
+    HostForm f(st);
+    f.up_secret(dB, blind, bb);
+    f.up(dP, pk, k ? n * sb : 0);
+    f.up(dH, h, k ? n * sb : 0);
+    f.launch([&] {
+        return launch_sigreq_init(c, n, q, k, dH.as<uint8_t>(), dP.as<uint8_t>(), dB.as<uint8_t>(), dO.as<uint8_t>(), st);
+    });
+    f.down(out_proofs, dO, pb);
     // the device copies of the blindings and of the digits of b2_i and hb_i are zeroed
-    bool wiped = hipMemsetAsync(dB.p, 0, bb, st) == hipSuccess;
-    if (k) wiped = hipMemsetAsync(c->rq_dig.p, 0, cck_rq_digit_bytes(n, (int)k), st) == hipSuccess && wiped;
-    if (hipStreamSynchronize(st) != hipSuccess || !wiped) return s ? s : CC_ERR_HIP;
-    return s;
+    f.wipe(c->rq_dig, k ? cck_rq_digit_bytes(n, (int)k) : 0);
+    return f.finish();
 }
 
 cc_status cc_sigreq_pok_gen_proof_batch_device(cc_ctx* c, size_t n, size_t q, size_t k, const uint8_t* d_msgs,
@@ -2644,25 +2429,19 @@ cc_status cc_sigreq_pok_gen_proof_batch(cc_ctx* c, size_t n, size_t q, size_t k,
     if (c->in_msgs.ensure(mb + 16) || dR.ensure(rb) || dB.ensure(bb) || dK.ensure(n * 48) || dC.ensure(n * 48) ||
         dO.ensure(pb))
         return CC_ERR_HIP;
-    auto run = [&]() -> cc_status {
-        if (k) HIPCK(hipMemcpyAsync(c->in_msgs.p, msgs, mb, hipMemcpyHostToDevice, st));
-        HIPCK(hipMemcpyAsync(dR.p, rand, rb, hipMemcpyHostToDevice, st));
-        HIPCK(hipMemcpyAsync(dB.p, blind, bb, hipMemcpyHostToDevice, st));
-        HIPCK(hipMemcpyAsync(dK.p, sk, n * 48, hipMemcpyHostToDevice, st));
-        HIPCK(hipMemcpyAsync(dC.p, chal, n * 48, hipMemcpyHostToDevice, st));
-        HIPCK(hipMemcpyAsync(dO.p, proofs, pb, hipMemcpyHostToDevice, st));
-        KCK(cck_rq_responses(sig_group(c->mode), n, (int)q, (int)k, c->in_msgs.as<uint8_t>(), dR.as<uint8_t>(),
-                             dB.as<uint8_t>(), dK.as<uint8_t>(), dC.as<uint8_t>(), dO.as<uint8_t>(), st));
-        HIPCK(hipMemcpyAsync(proofs, dO.p, pb, hipMemcpyDeviceToHost, st));
-        return CC_OK;
-    };
-    s = run();
-    // the device copies of the messages, r and the k_i, the blindings and the ElGamal key are zeroed
-    bool wiped = hipMemsetAsync(dR.p, 0, rb, st) == hipSuccess && hipMemsetAsync(dB.p, 0, bb, st) == hipSuccess &&
-                 hipMemsetAsync(dK.p, 0, n * 48, st) == hipSuccess;
-    if (k) wiped = hipMemsetAsync(c->in_msgs.p, 0, mb, st) == hipSuccess && wiped;
-    if (hipStreamSynchronize(st) != hipSuccess || !wiped) return s ? s : CC_ERR_HIP;
-    return s;
+    HostForm f(st);
+    f.up_secret(c->in_msgs, msgs, k ? mb : 0);
+    f.up_secret(dR, rand, rb);
+    f.up_secret(dB, blind, bb);
+    f.up_secret(dK, sk, n * 48);
+    f.up(dC, chal, n * 48);
+    f.up(dO, proofs, pb);
+    f.launch([&] {
+        return cck_rq_responses(sig_group(c->mode), n, (int)q, (int)k, c->in_msgs.as<uint8_t>(), dR.as<uint8_t>(),
+                                dB.as<uint8_t>(), dK.as<uint8_t>(), dC.as<uint8_t>(), dO.as<uint8_t>(), st);
+    });
+    f.down(proofs, dO, pb);
+    return f.finish();  // zeroes the device copies of the messages, r and the k_i, the blindings and the ElGamal key
 }
 
 // ---------------------------------------------------------------- keygen: dealing and the DVSS combine (keygen.hip)
@@ -2686,40 +2465,20 @@ cc_status cc_set_keygen_params(cc_ctx* c, const uint8_t* g_tilde, const uint8_t*
     const int og = oth_group(c->mode);
     const bool gh = vss_g != nullptr;
     auto tbytes = [&](int w) { return (tab_words(og, w) + (gh ? 2 * tab_words(1, w) : 0)) * 4; };
-    // the old tables are released first so their memory counts as free (identical calls pick the same width)
     c->kg_gt_table.release();
     c->kg_gh_table.release();
-    const double budget = std::min(kKgTableBudget, 0.5 * (double)free_hbm());
-    int wb = 8;
-    if (table_bits) {
-        wb = table_bits;
-    } else {
-        for (int cand : {16, 13, 12, 10})
-            if ((double)tbytes(cand) <= budget) {
-                wb = cand;
-                break;
-            }
-    }
+    int wb = pick_table_bits(table_bits, kKgTableBudget, tbytes);
     if (c->kg_gt_aff.ensure(aff_words(og) * 4) || c->kg_gt_inf.ensure(4) || c->kg_gh_aff.ensure(2 * aff_words(1) * 4) ||
         c->kg_gh_inf.ensure(2 * 4))
         return CC_ERR_HIP;
-    const double fr = (double)free_hbm();
-    if (fr > 0 && (double)tbytes(wb) > 0.9 * fr) {  // see rebuild_tables
-        if (table_bits || wb == 8) return CC_ERR_HIP;
-        wb = 8;
-    }
-    auto alloc = [&](int w) {
-        return c->kg_gt_table.ensure(tab_words(og, w) * 4) == 0 &&
-               (!gh || c->kg_gh_table.ensure(2 * tab_words(1, w) * 4) == 0);
-    };
-    if (!alloc(wb)) {
-        (void)hipGetLastError();  // clear the failed allocation's error
-        c->kg_gt_table.release();
+    wb = alloc_tables(wb, table_bits != 0, tbytes, [&](int w) {
+        if (c->kg_gt_table.ensure(tab_words(og, w) * 4) == 0 && (!gh || c->kg_gh_table.ensure(2 * tab_words(1, w) * 4) == 0))
+            return true;
+        c->kg_gt_table.release();  // neither without the other
         c->kg_gh_table.release();
-        if (table_bits || wb == 8) return CC_ERR_HIP;
-        wb = 8;  // the wide tables did not fit the free HBM
-        if (!alloc(wb)) return CC_ERR_HIP;
-    }
+        return false;
+    });
+    if (!wb) return CC_ERR_HIP;
     cc_status s = decode_points_host(c, og, 1, g_tilde, c->kg_gt_aff.as<uint32_t>(), c->kg_gt_inf.as<uint32_t>());
     if (s) return s;
     DevBuf pw;
@@ -2738,7 +2497,6 @@ cc_status cc_set_keygen_params(cc_ctx* c, const uint8_t* g_tilde, const uint8_t*
                             c->kg_gh_table.as<uint32_t>(), 1, c->stream));
         HIPCK(hipStreamSynchronize(c->stream));
     }
-    pw.release();
     c->kg_wbits = wb;
     c->kg_have_gh = gh;
     c->have_kg = true;
@@ -2815,37 +2573,25 @@ cc_status cc_keygen_deal_batch(cc_ctx* c, size_t m, size_t q, size_t t, size_t t
     if (B[0].ensure(cb) || B[2].ensure(xb) || B[3].ensure(yb + 16) || B[7].ensure(Xb) || B[8].ensure(Yb + 16))
         return CC_ERR_HIP;
     if (ped && (B[1].ensure(cb) || B[4].ensure(xb) || B[5].ensure(yb + 16) || B[6].ensure(mb))) return CC_ERR_HIP;
-    auto run = [&]() -> cc_status {
-        HIPCK(hipMemcpyAsync(B[0].p, coeffs, cb, hipMemcpyHostToDevice, st));
-        if (ped) HIPCK(hipMemcpyAsync(B[1].p, coeffs_t, cb, hipMemcpyHostToDevice, st));
-        cc_status e = launch_kg_deal(c, m, q, t, total, B[0].as<uint8_t>(), ped ? B[1].as<uint8_t>() : nullptr,
-                                     B[2].as<uint8_t>(), B[3].as<uint8_t>(), B[4].as<uint8_t>(), B[5].as<uint8_t>(),
-                                     B[6].as<uint8_t>(), B[7].as<uint8_t>(), B[8].as<uint8_t>(), st);
-        if (e) return e;
-        HIPCK(hipMemcpyAsync(out_x, B[2].p, xb, hipMemcpyDeviceToHost, st));
-        HIPCK(hipMemcpyAsync(out_X, B[7].p, Xb, hipMemcpyDeviceToHost, st));
-        if (q) {
-            HIPCK(hipMemcpyAsync(out_y, B[3].p, yb, hipMemcpyDeviceToHost, st));
-            HIPCK(hipMemcpyAsync(out_Y, B[8].p, Yb, hipMemcpyDeviceToHost, st));
-        }
-        if (ped) {
-            HIPCK(hipMemcpyAsync(out_xt, B[4].p, xb, hipMemcpyDeviceToHost, st));
-            if (q) HIPCK(hipMemcpyAsync(out_yt, B[5].p, yb, hipMemcpyDeviceToHost, st));
-            HIPCK(hipMemcpyAsync(out_comm, B[6].p, mb, hipMemcpyDeviceToHost, st));
-        }
-        return CC_OK;
-    };
-    s = run();
-    // the device copies of the coefficients and of the shares are zeroed (the kernels keep the window digits
-    // in registers: there is no digit scratch)
-    bool wiped = hipMemsetAsync(B[0].p, 0, cb, st) == hipSuccess && hipMemsetAsync(B[2].p, 0, xb, st) == hipSuccess;
-    if (q) wiped = hipMemsetAsync(B[3].p, 0, yb, st) == hipSuccess && wiped;
-    if (ped) {
-        wiped = hipMemsetAsync(B[1].p, 0, cb, st) == hipSuccess && hipMemsetAsync(B[4].p, 0, xb, st) == hipSuccess && wiped;
-        if (q) wiped = hipMemsetAsync(B[5].p, 0, yb, st) == hipSuccess && wiped;
-    }
-    if (hipStreamSynchronize(st) != hipSuccess || !wiped) return s ? s : CC_ERR_HIP;
-    return s;
+    const size_t pxb = ped ? xb : 0, pyb = ped ? yb : 0;  // the Pedersen buffers' sizes: nothing without them
+    HostForm f(st);
+    f.up_secret(B[0], coeffs, cb);
+    f.up_secret(B[1], coeffs_t, ped ? cb : 0);
+    f.launch([&] {
+        return launch_kg_deal(c, m, q, t, total, B[0].as<uint8_t>(), ped ? B[1].as<uint8_t>() : nullptr,
+                              B[2].as<uint8_t>(), B[3].as<uint8_t>(), B[4].as<uint8_t>(), B[5].as<uint8_t>(),
+                              B[6].as<uint8_t>(), B[7].as<uint8_t>(), B[8].as<uint8_t>(), st);
+    });
+    f.down_secret(out_x, B[2], xb);
+    f.down(out_X, B[7], Xb);
+    f.down_secret(out_y, B[3], yb);
+    f.down(out_Y, B[8], Yb);
+    f.down_secret(out_xt, B[4], pxb);
+    f.down_secret(out_yt, B[5], pyb);
+    f.down(out_comm, B[6], ped ? mb : 0);
+    // zeroes the device copies of the coefficients and of the shares (the kernels keep the window digits in
+    // registers: there is no digit scratch)
+    return f.finish();
 }
 
 static cc_status launch_kg_combine(cc_ctx* c, size_t m, size_t d, size_t q, size_t t, size_t total, bool ped,
@@ -2916,47 +2662,27 @@ cc_status cc_keygen_combine_batch(cc_ctx* c, size_t m, size_t d, size_t q, size_
     if (ped && (B[2].ensure(d * xb) || B[3].ensure(d * yb + 16) || B[4].ensure(d * mb) || B[7].ensure(xb) ||
                 B[8].ensure(yb + 16) || B[9].ensure(mb)))
         return CC_ERR_HIP;
-    auto run = [&]() -> cc_status {
-        HIPCK(hipMemcpyAsync(B[0].p, x, d * xb, hipMemcpyHostToDevice, st));
-        if (q) HIPCK(hipMemcpyAsync(B[1].p, y, d * yb, hipMemcpyHostToDevice, st));
-        if (ped) {
-            HIPCK(hipMemcpyAsync(B[2].p, xt, d * xb, hipMemcpyHostToDevice, st));
-            if (q) HIPCK(hipMemcpyAsync(B[3].p, yt, d * yb, hipMemcpyHostToDevice, st));
-            HIPCK(hipMemcpyAsync(B[4].p, comm, d * mb, hipMemcpyHostToDevice, st));
-        }
-        cc_status e = launch_kg_combine(c, m, d, q, t, total, ped, B[0].as<uint8_t>(), B[1].as<uint8_t>(),
-                                        B[2].as<uint8_t>(), B[3].as<uint8_t>(), B[4].as<uint8_t>(), B[5].as<uint8_t>(),
-                                        B[6].as<uint8_t>(), B[7].as<uint8_t>(), B[8].as<uint8_t>(), B[9].as<uint8_t>(),
-                                        B[10].as<uint8_t>(), B[11].as<uint8_t>(), st);
-        if (e) return e;
-        HIPCK(hipMemcpyAsync(out_x, B[5].p, xb, hipMemcpyDeviceToHost, st));
-        HIPCK(hipMemcpyAsync(out_X, B[10].p, Xb, hipMemcpyDeviceToHost, st));
-        if (q) {
-            HIPCK(hipMemcpyAsync(out_y, B[6].p, yb, hipMemcpyDeviceToHost, st));
-            HIPCK(hipMemcpyAsync(out_Y, B[11].p, Yb, hipMemcpyDeviceToHost, st));
-        }
-        if (ped) {
-            HIPCK(hipMemcpyAsync(out_xt, B[7].p, xb, hipMemcpyDeviceToHost, st));
-            if (q) HIPCK(hipMemcpyAsync(out_yt, B[8].p, yb, hipMemcpyDeviceToHost, st));
-            HIPCK(hipMemcpyAsync(out_comm, B[9].p, mb, hipMemcpyDeviceToHost, st));
-        }
-        return CC_OK;
-    };
-    s = run();
-    // the device copies of the dealers' shares and of the combined shares are zeroed
-    bool wiped = hipMemsetAsync(B[0].p, 0, d * xb, st) == hipSuccess && hipMemsetAsync(B[5].p, 0, xb, st) == hipSuccess;
-    if (q)
-        wiped = hipMemsetAsync(B[1].p, 0, d * yb, st) == hipSuccess && hipMemsetAsync(B[6].p, 0, yb, st) == hipSuccess &&
-                wiped;
-    if (ped) {
-        wiped = hipMemsetAsync(B[2].p, 0, d * xb, st) == hipSuccess && hipMemsetAsync(B[7].p, 0, xb, st) == hipSuccess &&
-                wiped;
-        if (q)
-            wiped = hipMemsetAsync(B[3].p, 0, d * yb, st) == hipSuccess &&
-                    hipMemsetAsync(B[8].p, 0, yb, st) == hipSuccess && wiped;
-    }
-    if (hipStreamSynchronize(st) != hipSuccess || !wiped) return s ? s : CC_ERR_HIP;
-    return s;
+    const size_t pxb = ped ? xb : 0, pyb = ped ? yb : 0;  // the Pedersen buffers' sizes: nothing without them
+    HostForm f(st);
+    f.up_secret(B[0], x, d * xb);
+    f.up_secret(B[1], y, d * yb);
+    f.up_secret(B[2], xt, d * pxb);
+    f.up_secret(B[3], yt, d * pyb);
+    f.up(B[4], comm, ped ? d * mb : 0);
+    f.launch([&] {
+        return launch_kg_combine(c, m, d, q, t, total, ped, B[0].as<uint8_t>(), B[1].as<uint8_t>(), B[2].as<uint8_t>(),
+                                 B[3].as<uint8_t>(), B[4].as<uint8_t>(), B[5].as<uint8_t>(), B[6].as<uint8_t>(),
+                                 B[7].as<uint8_t>(), B[8].as<uint8_t>(), B[9].as<uint8_t>(), B[10].as<uint8_t>(),
+                                 B[11].as<uint8_t>(), st);
+    });
+    f.down_secret(out_x, B[5], xb);
+    f.down(out_X, B[10], Xb);
+    f.down_secret(out_y, B[6], yb);
+    f.down(out_Y, B[11], Yb);
+    f.down_secret(out_xt, B[7], pxb);
+    f.down_secret(out_yt, B[8], pyb);
+    f.down(out_comm, B[9], ped ? mb : 0);
+    return f.finish();  // zeroes the device copies of the dealers' shares and of the combined shares
 }
 
 // ---------------------------------------------------------------- issuer side, device forms (issue_dev.hip)
@@ -3036,7 +2762,8 @@ cc_status cc_blind_sign_batch_device(cc_ctx* c, size_t n, size_t q, size_t k, co
         s = launch_issuer_h(c, n, q, k, d_commitment, d_known, d_out_h, st);
         if (s) return s;
     }
-    auto run = [&]() -> cc_status {
+    HostForm f(st, /*sync=*/false);  // a device form: the work and the wipes stay queued on the caller's stream
+    f.launch([&]() -> cc_status {
         // x | y through the pinned ring: the caller's arrays are free again when the call returns
         std::vector<uint8_t> xy(xyb);
         memcpy(xy.data(), x, 48);
@@ -3052,15 +2779,13 @@ cc_status cc_blind_sign_batch_device(cc_ctx* c, size_t n, size_t q, size_t k, co
         KCK(cck_copy_rows(n, sb, c->bs_out.as<uint8_t>(), 2 * sb, d_out_c1, st));
         KCK(cck_copy_rows(n, sb, c->bs_out.as<uint8_t>() + sb, 2 * sb, d_out_c2, st));
         return CC_OK;
-    };
-    s = run();
+    });
     // queued behind the work: the device copies of x | y, of the tasks' scalars (y_i, x + sum y m) and of
     // their digits (the Straus scratch) are zeroed
-    const bool wiped = hipMemsetAsync(c->bs_xy.p, 0, xyb, st) == hipSuccess &&
-                       hipMemsetAsync(c->bs_sc.p, 0, 2 * n * t * 32, st) == hipSuccess &&
-                       hipMemsetAsync(c->agg_scratch.p, 0, scr, st) == hipSuccess;
-    if (!wiped) return s ? s : CC_ERR_HIP;
-    return s;
+    f.wipe(c->bs_xy, xyb);
+    f.wipe(c->bs_sc, 2 * n * t * 32);
+    f.wipe(c->agg_scratch, scr);
+    return f.finish();
 }
 
 // ---------------------------------------------------------------- device sets + RCCL

@@ -11,6 +11,7 @@
 #include <cstdlib>
 #include <cstring>
 #include "codec.h"
+#include "launch.h"
 #include "lazy.h"  // LZ_ONE_LIMBS (k_wide_pairs)
 #include "tower_q.h"  // lz::fp_inv_int_quad (the wide forms' inversions)
 #include "tower_pl.h"
@@ -1364,9 +1365,6 @@ extern "C" int cck_f12_reduce_wide(size_t n, const uint32_t* d_in, uint32_t* d_o
 static inline unsigned nblocks(size_t n, unsigned bs) { return (unsigned)((n + bs - 1) / bs); }
 
 // the batched kernel: lazy field, one credential per lane quad, the chain in registers (fexp_q.hip)
-extern "C" int cck_fexp_q(size_t n, const uint32_t* d_f, const uint32_t* d_flags, uint8_t* d_verdicts, uint8_t* d_gt,
-                          hipStream_t st);
-
 // n <= wide_max (the caller's threshold; d_scratch >= 72 x 12 x n words): one wave per element, the
 // latency-bound form (k_fexp1); otherwise the quad-lane batch kernel
 extern "C" int cck_fexp(size_t n, uint32_t* d_f, uint32_t* d_scratch, const uint32_t* d_flags, uint8_t* d_verdicts,

@@ -9,6 +9,7 @@
 // scratch round trips between steps (the pair layout's chain rested every Fp12 in an 84-slot HBM
 // scratch and reloaded it for the next step).
 #include "codec.h"
+#include "launch.h"
 #include "tower_q.h"
 
 namespace cc {

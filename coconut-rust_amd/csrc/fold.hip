@@ -34,6 +34,7 @@
 #include "codec.h"
 #include "curve_pl.h"
 #include "fixed.h"
+#include "launch.h"
 #include "rlc_part.h"
 #include "soa.h"
 

@@ -11,6 +11,7 @@
 // Restated from recalled AMCL v3.2 sources (not in this container): PARITY UNPINNED; the CPU mirror
 // is oracle/hash_to_curve.py.
 #include "codec.h"
+#include "launch.h"
 #include "subgroup.h"
 
 using namespace cc;

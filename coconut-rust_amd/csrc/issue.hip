@@ -14,6 +14,7 @@
 //     checks with the response-equality rule proof_2.responses[1] == proof_commitment.responses[i].
 #include "codec.h"
 #include "fr.h"
+#include "launch.h"
 #include "sigreq_layout.h"  // ProofLayout: the proof record of cc_sigreq_verify_batch
 
 using namespace cc;

@@ -23,6 +23,7 @@
 //   The verdict is then issue.hip k_sigreq_combine's: a request passes iff its checks passed and
 //   r_2b[i] == r_comm[i] as Fr values.
 #include "fixed.h"
+#include "launch.h"
 #include "prove_common.h"
 #include "sigreq_layout.h"
 

@@ -14,6 +14,7 @@
 // or SigG1 (sigma in G1, vk in G2).
 #include "codec.h"
 #include "fixed.h"
+#include "launch.h"
 #include "pairing.h"
 #include "soa.h"
 #include "subgroup.h"

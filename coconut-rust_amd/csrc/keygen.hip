@@ -32,6 +32,7 @@
 //   per call, download): 8.4x / 11.1x at the first shape, 14.2x / 29.7x at the second; spreads below 1 % (the
 //   yardstick's below 3 %).
 #include "fixed.h"
+#include "launch.h"
 #include "prove_common.h"
 
 using namespace cc;

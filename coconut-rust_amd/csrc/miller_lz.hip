@@ -29,6 +29,7 @@
 #endif
 #include "codec.h"
 #include "curve_pl.h"
+#include "launch.h"
 #include "tower_lz.h"
 
 namespace cc {

@@ -23,6 +23,7 @@
 #include "curve_wide_lz.h"
 #include "fixed.h"
 #include "fr.h"
+#include "launch.h"
 #include "pairing.h"
 #include "soa.h"
 #include "straus.h"

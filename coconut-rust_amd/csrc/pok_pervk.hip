@@ -32,6 +32,7 @@
 #include "curve_lz.h"
 #include "curve_pl.h"
 #include "fr.h"
+#include "launch.h"
 #include "pairing.h"
 #include "soa.h"
 #include "straus.h"

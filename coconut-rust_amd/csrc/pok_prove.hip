@@ -16,6 +16,7 @@
 //   unblind: k_unblind_assemble lays (c1, c2) and (-sk, 1) out for the windowed Straus MSM
 //     (aggregate.hip k_msm_straus, t = 2).
 #include "fixed.h"
+#include "launch.h"
 #include "prove_common.h"
 
 using namespace cc;

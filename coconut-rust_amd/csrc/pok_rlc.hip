@@ -28,6 +28,7 @@
 #include "curve_pl.h"
 #include "fixed.h"
 #include "fr.h"
+#include "launch.h"
 #include "pairing.h"
 #include "soa.h"
 #include "subgroup.h"

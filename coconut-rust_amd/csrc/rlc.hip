@@ -28,6 +28,7 @@
 #include "curve_pl.h"
 #include "fixed.h"
 #include "fr.h"
+#include "launch.h"
 #include "pairing.h"
 #include "rlc_part.h"
 #include "soa.h"
@@ -311,8 +312,6 @@ __global__ __launch_bounds__(256) void k_rlc_gather(size_t k, const uint32_t* __
 }
 
 static inline unsigned nblocks(size_t n, unsigned bs) { return (unsigned)((n + bs - 1) / bs); }
-
-extern "C" int cck_f12_reduce_wide(size_t n, const uint32_t* d_in, uint32_t* d_out, hipStream_t st);
 
 // levels with at most this many products run in the wide form (one wave a product): the packed form
 // holds ~47 us a level (one product's latency on one lane pair) up to 16,384 products, the wide form

@@ -21,6 +21,7 @@
 //     record (sigreq_layout.h).
 //   k_rq_h_rows lays commitment || known messages out as compute_h's input rows.
 #include "fixed.h"
+#include "launch.h"
 #include "prove_common.h"
 #include "sigreq_layout.h"
 

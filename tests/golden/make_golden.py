@@ -601,6 +601,9 @@ def main():
         for mode in ("G2", "G1"):
             write(f"issuance_{mode.lower()}.json", {"cases": [make_issuance(mode, 6, 2, 7, 21), make_issuance(mode, 4, 0, 3, 22),
                                                               make_issuance(mode, 3, 3, 3, 23)]})
+    if want("hostforms"):  # the smallest shapes with a hidden and a known message (tests/test_gpu_host_forms.py)
+        write("host_forms.json", {"issuance": {m: make_issuance(m, 2, 1, 3, 51) for m in ("G2", "G1")},
+                                  "keygen": make_keygen(52, t=2, n=3, q=1)})
     if want("h2c"):
         write("hash_to_curve.json", make_hash_to_curve())
     if want("h2cedges"):

@@ -8,6 +8,9 @@
   HIP streams and events) is compiled with the same sanitizers against a simulated device timeline
   (tests/host/test_slots.cpp): a workspace set missing a member must be refused, a slot's buffers must not
   be reallocated while its batch is queued, and a launch failing half-way must still fence its slot.
+* The owned device buffers and the host forms' sequence (coconut-rust_amd/csrc/devbuf.h: upload, launch,
+  download, wipe, synchronise) are compiled the same way against a simulated device that logs every
+  operation and can fail any one of them (tests/host/test_devbuf.cpp), with LeakSanitizer on.
 """
 import os
 import subprocess
@@ -28,6 +31,17 @@ def test_slot_bookkeeping_under_asan_ubsan(tmp_path):
     subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Wextra", "-Werror", *SAN, "-I",
                            os.path.join(ROOT, "coconut-rust_amd", "csrc"),
                            os.path.join(ROOT, "tests", "host", "test_slots.cpp"), "-o", exe])
+    p = subprocess.run([exe], capture_output=True, text=True, env=_san_env())
+    assert p.returncode == 0, p.stdout + p.stderr
+    assert "all checks passed" in p.stdout
+    assert "Sanitizer" not in p.stderr and "runtime error" not in p.stderr
+
+
+def test_devbuf_and_host_form_sequence_under_asan_ubsan(tmp_path):
+    exe = str(tmp_path / "test_devbuf")
+    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Wextra", "-Werror", *SAN, "-I",
+                           os.path.join(ROOT, "coconut-rust_amd", "csrc"),
+                           os.path.join(ROOT, "tests", "host", "test_devbuf.cpp"), "-o", exe])
     p = subprocess.run([exe], capture_output=True, text=True, env=_san_env())
     assert p.returncode == 0, p.stdout + p.stderr
     assert "all checks passed" in p.stdout
