@@ -92,3 +92,31 @@ def test_divstep_inversions_on_device():
         want = pow(v, P - 2, P)
         assert words(one[k]) == want, k
         assert all(words(four[4 * k + j]) == want for j in range(4)), k
+
+
+def test_canon_on_device():
+    """lazy.h canon (behind every is_zero, eq, inversion input and GT byte) against value % p at the bounds
+    its type allows (limbs below 2047 x 2^20, |value| < 2048 p), and on values congruent to 0 or +-1 whose
+    limbs are not: k p, k p + 1, k p - 1 for k up to +-2047, each once in normalised limbs and once with
+    multiples of 2^28 moved between neighbouring limbs (large and negative limbs, the same value)."""
+    rng = random.Random(29)
+    xs = [rand_lz(2047, 32768, rng, extreme=k % 2 == 0) for k in range(982)]
+    edge = [k * P + d for k in (0, 1, -1, 2, -2, 2047, -2047) for d in (0, 1, -1)]
+    for v in edge:
+        norm = [(v >> (28 * k)) & M28 for k in range(LN - 1)] + [v >> (28 * (LN - 1))]
+        red = list(norm)
+        for k in range(LN - 1):
+            m = rng.randrange(-7, 7)
+            red[k] += m << 28
+            red[k + 1] -= m
+        assert value(norm) == v and value(red) == v and red != norm
+        assert any(t < 0 for t in red[:-1]) and any(t > M28 for t in red[:-1])
+        xs += [norm, red]
+    assert len(xs) == 1024
+    assert all(abs(t) < (2047 << 20) for x in xs for t in x) and all(abs(value(x)) < 2048 * P for x in xs)
+    out = _run(6, xs)
+    words = lambda row: sum((t & 0xFFFFFFFF) << (32 * k) for k, t in enumerate(row[:12]))  # noqa: E731
+    for x, r in zip(xs, out):
+        assert words(r) == value(x) % P and r[12:] == [0, 0]
+    for r in out[982::6] + out[983::6]:  # the k p rows: all-zero words
+        assert r == [0] * LN
