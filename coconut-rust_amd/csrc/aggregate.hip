@@ -10,7 +10,7 @@
 //   k_prep_pok     : ps_sig PoKOfSignatureProof::verify [EXT] (reference pok_sig.rs:103-105):
 //                    Schnorr check MSM(g~, Y~_hidden.., J; responses.., chal) == T, then
 //                    J' = X~ + J + sum_revealed Y~_i m_i, written in the verify kernels' Miller-loop
-//                    operand layout so k_miller_* / k_fexp finish the 2-pairing check.
+//                    operand layout so k_miller_* / cck_fexp finish the 2-pairing check.
 #include <cmath>
 #include <cstdlib>
 

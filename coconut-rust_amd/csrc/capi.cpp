@@ -676,8 +676,8 @@ cc_status cc_table_bits(const cc_ctx* c, int* verkey_bits, int* issuer_bits) {
     return CC_OK;
 }
 
-// Small batches run latency-bound: their Miller loops one wave per pair (n <= kWideMax: fexp_pl.hip
-// k_wide_pairs -> k_miller_wide -> k_f12_reduce_wide) instead of one lane pair per credential (k_miller:
+// Small batches run latency-bound: their Miller loops one wave per pair (n <= kWideMax: miller_wide.hip
+// k_wide_pairs -> k_miller_wide -> fexp_pl.hip k_f12_reduce_wide) instead of one lane pair per credential (k_miller:
 // one 2-pair loop's latency on a lone wave, ~7.5 ms for any batch up to a few thousand), and their
 // final exponentiation one wave per credential (n <= kFexpWideMax: k_fexp1, 1.33 ms) instead of a lane
 // quad (k_fexp_q: ~3 ms floor).  Both wide kernels hold one wave a SIMD: 1,024 waves a round of the
@@ -687,7 +687,7 @@ cc_status cc_table_bits(const cc_ctx* c, int* verkey_bits, int* issuer_bits) {
 // kFexpWideMax, the PoK and per-credential-verkey preps up to kPrepWideMax.  Measured:
 // profiles/r05/wide_spread, thresholds, miller_wide_pipe, fexp_thr.
 // (the thresholds live in slots.h with the workspace sizes they decide; k_miller_wide2, two waves a
-// pair, takes launches of <= kWide2Max = 256 pairs, i.e. <= 128 credentials: fexp_pl.hip)
+// pair, takes launches of <= kWide2Max = 256 pairs, i.e. <= 128 credentials: miller_wide.hip)
 using cc::slots::kFexpWideMax;
 using cc::slots::kPrepWideMax;
 using cc::slots::kWideMax;

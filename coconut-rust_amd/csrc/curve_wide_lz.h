@@ -204,7 +204,7 @@ DEV void jg_to_aff_rp(Fp& x, Fp& y, const JG& p) {
 }
 
 // curve.h jac_to_aff for a pair-lane G2 point every pair holds alike (storage form): the Fp2 inversion's
-// norm inverted in the quad divstep form, as fexp_pl.hip f2_inv_q
+// norm inverted in the quad divstep form, as tower_wide.h f2_inv_q
 DEV bool jac_to_aff(Aff<pl::Fp2>& r, const Jac<pl::Fp2>& p) {
     if (cc::jac_is_inf(p)) {
         pl::f2_zero(r.x);

@@ -36,7 +36,8 @@ __device__ unsigned long long* fq_prof_acc() {
 namespace {
 
 // ---------------------------------------------------------------- compressed cyclotomic squaring
-// fexp_pl.hip cyc4_sqr (Karabina's compression restated for this tower) on b = b0 + b1 s, c = c0 + c1 s:
+// Karabina's compression restated for this tower (derivation: fexp_pl.hip, above cyc4_sqr_dist_lz) on
+// b = b0 + b1 s, c = c0 + c1 s:
 //     b0' = 3 (2 xi c0 c1) + 2 b0    b1' = 3 (c0^2 + xi c1^2) - 2 b1
 //     c0' = 3 (b0^2 + xi b1^2) - 2 c0    c1' = 3 (2 b0 b1) + 2 c1
 // Pair 0 holds V = c0, W = b0; pair 1 V = b1, W = c1.  Each lane squares S1 = V, S2 = W and S3 = W + V'
@@ -69,7 +70,7 @@ DEV void qz_sqr(QZ& x) {
     x.V = reduce(add(T, dbl(sub(T, x.V))));
     x.W = reduce(add(Xs, dbl(add(Xs, x.W))));
 }
-// numerator of this lane's a_j and the common denominator D (fexp_pl.hip cyc4_num):
+// numerator of this lane's a_j and the common denominator D (as fexp_pl.hip decompress3_wide):
 //     a0 = (b0 Nb + xi c1 Nc) / D,  a1 = (c0 Nc + b1 Nb) / D,
 //     Nb = b0^2 - xi b1^2,  Nc = c0^2 - xi c1^2,  D = 2 (b0 c0 - xi b1 c1)
 DEV void qz_num(F2R& nj, F2R& den, const QZ& z) {

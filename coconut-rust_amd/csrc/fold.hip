@@ -29,7 +29,7 @@
 //   k_fold_fixed<F>                             : the fixed points P_w (once per verkey, cck_fold_fixed)
 // X_i = -sigma_2,i (AoS affine in the lazy field's form, fixed.h fp_to_lazy_form; written by the RLC
 // prep); S_w lands in the shard's partial (rlc_part.h: affine words + identity flag per window), and
-// the finish pairs every shard's S_w with P_w (rlc.hip k_rlc_gather, then k_miller_wide): SigG2 S in
+// the finish pairs every shard's S_w with P_w (rlc.hip k_rlc_gather, then miller_wide.hip k_miller_wide): SigG2 S in
 // G2 (the Q side), SigG1 S in G1 (the P side), P_w on the other side.
 #include "codec.h"
 #include "curve_pl.h"

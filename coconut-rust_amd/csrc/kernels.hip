@@ -9,7 +9,7 @@
 //   k_prep_*   : decode sigma/messages, fixed-base (shared vk) MSM, write the Miller-loop operands
 //                (SoA, limb-major: coalesced per limb); per-credential verkeys: pervk.hip
 //   k_miller_* : shared-squaring 2-pair Miller loop -> f (Fp12, SoA)
-//   k_fexp     : final exponentiation, is_one, identity check -> verdict (+ optional GT bytes)
+//   cck_fexp   : final exponentiation, is_one, identity check -> verdict (+ optional GT bytes)
 // Group assignment is a template parameter: kSigG2 (reference default, sigma in G2, vk in G1)
 // or SigG1 (sigma in G1, vk in G2).
 #include "codec.h"

@@ -1,7 +1,7 @@
 // Miller-loop kernels for gfx950 on the lazy radix-2^28 field (lazy.h, tower_lz.h) — the
 // shared-squaring 2-pair loop of ate_2_pairing (ps_sig `ate_2_pairing` -> AMCL `pair::ate2`,
-// reference src/lib.rs:13).  Replaces miller_pl.hip (same launchers, same SoA
-// inputs and outputs); one credential per PAIR of adjacent lanes as there.
+// reference src/lib.rs:13); one credential per PAIR of adjacent lanes (the layout of
+// tower_pl.h).
 //
 //   SigG2: pair 0 = (sigma_1, pr) with pr in Jacobian-evaluation form (XZ, Y, Z^3);
 //          pair 1 = (-sigma_2, g~): g~ affine constant.
@@ -12,7 +12,7 @@
 //   credentials through the 2-pair loop, is the round-3 form): the RLC only needs the product of the
 //   credentials' Miller values, and the shared squaring divides the Fp12 work per credential (5,002 Fp
 //   multiplications against 5,548 for two a loop, 6,664 for a loop of its own).  The fold's 16 window
-//   pairs run in the finish in the wide one-wave form (fexp_pl.hip k_miller_wide).
+//   pairs run in the finish in the wide one-wave form (miller_wide.hip k_miller_wide).
 //
 // Representation boundary: the prep SoA holds canonical 12 x 32 values in R = 2^406 form.  The twist
 // points are moved to R' form once (in_r: T's start and the addition steps' Q).  The G1 evaluation
@@ -20,7 +20,7 @@
 // coefficient of a line comes out scaled by the same 2^14 (R / R'), and affine points use the constant
 // R mod p as their Z; a line scaled by an Fp constant leaves the pairing unchanged (the final
 // exponentiation's easy part kills Fp^*), as does the doubling step's 4x scale of T (lines are
-// homogeneous of degree 2 in T).  The Miller value leaves in R form, canonical (out_r), for k_fexp.
+// homogeneous of degree 2 in T).  The Miller value leaves in R form, canonical (out_r), for cck_fexp.
 #ifndef CC_MILLER_SIG
 #define CC_MILLER_SIG 2
 #endif

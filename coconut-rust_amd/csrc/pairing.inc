@@ -1,43 +1,8 @@
-// Optimal-ate pieces written only in terms of the tower primitives (f2_*, f4_*, f12_*, f2_half,
-// load_f2c): Frobenius maps, the sparse line multiply, the doubling/addition line functions and the
-// cyclotomic exponentiation by x.  Textually included inside namespace cc (pairing.h) and
-// cc::pl (tower_pl.h); see pairing.h for the algorithm notes.  No include guard.
-// x^p coefficient-wise: conj(c) * gamma_k for the coefficient of W^k.
-// AMCL slots -> W power: a.a 0, a.b 3, b.a 1, b.b 4, c.a 2, c.b 5.
-DEV void frob_coef(Fp2& c, int k) {
-    Fp2 g, t;
-    load_f2c(g, kGamma1[k]);
-    f2_conj(t, c);
-    f2_mul(c, t, g);
-}
-
-DEV void f12_frob(Fp12& r, const Fp12& x) {
-    r = x;
-    // a.a (k=0): gamma_0 = 1 -> conj only
-    f2_conj(r.a.a, r.a.a);
-    frob_coef(r.a.b, 3);
-    frob_coef(r.b.a, 1);
-    frob_coef(r.b.b, 4);
-    frob_coef(r.c.a, 2);
-    frob_coef(r.c.b, 5);
-}
-
-DEV void frob2_coef(Fp2& c, int k) {
-    Fp g;
-#pragma unroll
-    for (int j = 0; j < NL; j++) g.v[j] = kGamma2[k][j];
-    f2_mul_fp(c, c, g);
-}
-
-DEV void f12_frob2(Fp12& r, const Fp12& x) {
-    r = x;
-    frob2_coef(r.a.b, 3);
-    frob2_coef(r.b.a, 1);
-    frob2_coef(r.b.b, 4);
-    frob2_coef(r.c.a, 2);
-    frob2_coef(r.c.b, 5);
-}
-
+// Optimal-ate pieces written only in terms of the tower primitives (f2_*, f4_*, f12_*, f2_half):
+// the sparse line multiply and the doubling/addition line functions.  Textually included inside
+// namespace cc (pairing.h) and cc::pl (tower_pl.h); see pairing.h for the algorithm notes.  No include
+// guard.  (The Frobenius maps and the cyclotomic steps live with the towers that run them: tower_lz.h,
+// tower_q.h, tower_wide.h.)
 // ---------------------------------------------------------------- sparse line multiply
 // f *= (A + C w^2) with A = (l0, l3) in Fp4 and C = (l2, 0): 13 Fp2 multiplications.
 DEV void f12_mul_line(Fp12& f, const Fp2& l0, const Fp2& l2, const Fp2& l3) {
@@ -161,15 +126,3 @@ DEV void eval_line(Fp12& f, const Fp2& l0, const Fp2& l2c, const Fp2& l3c, const
     f2_mul_fp(a3, l3c, P.py);
     f12_mul_line(f, a0, a2, a3);
 }
-
-// ---------------------------------------------------------------- final exponentiation
-// y^|x| for cyclotomic y (square-and-multiply over the 64-bit constant), then conj: y^x.
-DEV void cyc_pow_x(Fp12& r, const Fp12& y) {
-    Fp12 acc = y;
-    for (int i = 62; i >= 0; i--) {
-        f12_cyc_sqr(acc, acc);
-        if ((X_ABS >> i) & 1ull) f12_mul(acc, acc, y);
-    }
-    f12_conj(r, acc);
-}
-

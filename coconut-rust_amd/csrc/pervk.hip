@@ -16,7 +16,7 @@
 //     affine in the R' form.
 //   SigG1 (verkey in G2): lane h decodes sigma_{h+1}; the pair runs the G2 Straus on the lazy pair-lane
 //     field over every Y~_j (straus_g2lz_pair) and adds X~.
-// The prep writes the SoA operands of kernels.hip's k_prep_*_pair, so k_miller / k_fexp finish.
+// The prep writes the SoA operands of kernels.hip's k_prep_*_pair, so k_miller / cck_fexp finish.
 #include "codec.h"
 #include "curve_lz.h"
 #include "curve_pl.h"

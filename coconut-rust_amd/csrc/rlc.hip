@@ -23,7 +23,7 @@
 //   k_rlc_partial_out                   : the partial's product and flag words (rlc_part.h; the fold
 //                                         writes its window section)
 //   k_rlc_gather                        : the finish's inputs from the gathered partials: their products
-//                                         and every shard's window pairs (S_w, P_w) for k_miller_wide
+//                                         and every shard's window pairs (S_w, P_w) for miller_wide.hip k_miller_wide
 #include "codec.h"
 #include "curve_pl.h"
 #include "fixed.h"

@@ -14,9 +14,6 @@ DEV void f4_sub(Fp4& r, const Fp4& x, const Fp4& y) { f2_sub(r.a, x.a, y.a); f2_
 DEV void f4_dbl(Fp4& r, const Fp4& x) { f2_dbl(r.a, x.a); f2_dbl(r.b, x.b); }
 DEV void f4_neg(Fp4& r, const Fp4& x) { f2_neg(r.a, x.a); f2_neg(r.b, x.b); }
 DEV void f4_conj(Fp4& r, const Fp4& x) { r.a = x.a; f2_neg(r.b, x.b); }  // a - b s
-// y - conj(x) and y + conj(x) without materialising conj(x) (one Fp2 op per half instead of two)
-DEV void f4_sub_conj(Fp4& r, const Fp4& y, const Fp4& x) { f2_sub(r.a, y.a, x.a); f2_add(r.b, y.b, x.b); }
-DEV void f4_add_conj(Fp4& r, const Fp4& y, const Fp4& x) { f2_add(r.a, y.a, x.a); f2_sub(r.b, y.b, x.b); }
 
 DEV void f4_mul(Fp4& r, const Fp4& x, const Fp4& y) {
     Fp2 t0, t1, s0, s1;
@@ -57,18 +54,6 @@ DEV void f4_mul_s(Fp4& r, const Fp4& x) {
 DEV void f4_mul_f2(Fp4& r, const Fp4& x, const Fp2& c) {
     f2_mul(r.a, x.a, c);
     f2_mul(r.b, x.b, c);
-}
-
-DEV void f4_inv(Fp4& r, const Fp4& x) {
-    Fp2 n, t;
-    f2_sqr(n, x.a);
-    f2_sqr(t, x.b);
-    f2_mul_xi(t, t);
-    f2_sub(n, n, t);  // a^2 - xi b^2
-    f2_inv(n, n);
-    f2_mul(r.a, x.a, n);
-    f2_mul(t, x.b, n);
-    f2_neg(r.b, t);
 }
 
 // ============================== Fp12 = Fp4[w]/(w^3 - s) ==============================
@@ -142,51 +127,4 @@ DEV void f12_sqr(Fp12& r, const Fp12& x) {
     f4_mul_s(t, t);
     f4_add(r.b, s1, t);
     r.a = ra;
-}
-
-// Granger-Scott squaring for elements of the cyclotomic subgroup (AMCL FP12::usqr):
-// a' = 3a^2 - 2 conj(a), b' = 3 s c^2 + 2 conj(b), c' = 3 b^2 - 2 conj(c)
-DEV void f12_cyc_sqr(Fp12& r, const Fp12& x) {
-    // ordered for low liveness: each output replaces its input as soon as that input is dead
-    // (r may alias x)
-    Fp4 A, t;
-    f4_sqr(A, x.a);
-    f4_sub_conj(t, A, x.a);
-    f4_dbl(t, t);
-    f4_add(r.a, t, A);
-    Fp4 B, C;
-    f4_sqr(C, x.b);
-    f4_sqr(B, x.c);
-    f4_mul_s(B, B);
-    f4_add_conj(t, B, x.b);
-    f4_dbl(t, t);
-    f4_add(r.b, t, B);
-    f4_sub_conj(t, C, x.c);
-    f4_dbl(t, t);
-    f4_add(r.c, t, C);
-}
-
-DEV void f12_inv(Fp12& r, const Fp12& x) {
-    Fp4 A, B, C, F, t;
-    f4_sqr(A, x.a);
-    f4_mul(t, x.b, x.c);
-    f4_mul_s(t, t);
-    f4_sub(A, A, t);  // a^2 - s bc
-    f4_sqr(B, x.c);
-    f4_mul_s(B, B);
-    f4_mul(t, x.a, x.b);
-    f4_sub(B, B, t);  // s c^2 - ab
-    f4_sqr(C, x.b);
-    f4_mul(t, x.a, x.c);
-    f4_sub(C, C, t);  // b^2 - ac
-    f4_mul(F, x.c, B);
-    f4_mul(t, x.b, C);
-    f4_add(F, F, t);
-    f4_mul_s(F, F);
-    f4_mul(t, x.a, A);
-    f4_add(F, F, t);
-    f4_inv(F, F);
-    f4_mul(r.a, A, F);
-    f4_mul(r.b, B, F);
-    f4_mul(r.c, C, F);
 }

@@ -148,7 +148,7 @@ DEV auto f12_mul_line(const F12<A, B>& f, const L0& l0, const L2& l2, const L3& 
 }
 
 
-// ---------------------------------------------------------------- Frobenius (pairing.inc), R' constants
+// ---------------------------------------------------------------- Frobenius (pairing.h kGamma1 / kGamma2), R' constants
 // gamma_k = xi^(k(p-1)/6) (a, b) and gamma2_k = xi^(k(p^2-1)/6) in Fp (tools/gen_lz_constants.py)
 struct F2cz {
     int32_t a[LN], b[LN];

@@ -580,6 +580,32 @@ def make_pairing_kat(seed):
     return {"pairings": out}
 
 
+def make_miller_wide_words():
+    """The wide Miller loop's own output words for the 16 pairs of tests/miller_wide_cases.py (k = 1, no
+    flags).  Unlike every other fixture this one is recorded from the device, not computed by the oracle:
+    it needs the built library and a GPU, so it is made only when asked for by name
+
+        python tests/golden/make_golden.py millerwide
+
+    and pins the representation of the Miller value (which the oracle does not define: any Fp* multiple
+    has the same GT) across changes of csrc/miller_wide.hip.  The 16 pairs run once as a launch of 16
+    (k_miller_wide2) and once as the first 16 of 257 (k_miller_wide); both kernels must write the same
+    words, which are stored once, 144 little-endian words in hex per pair."""
+    root = os.path.dirname(os.path.dirname(HERE))
+    sys.path[:0] = [os.path.join(root, "tests"), os.path.join(root, "coconut-rust_amd")]
+    import miller_wide_cases as M
+    import test_gpu_miller_wide_direct as T
+    K = T.launchers()
+    sets = []
+    for n in (16, 257):
+        lay = M.layout(n)
+        rc, words = T.run_miller(K, [M.pairs()[t] + (k,) for t, k, _ in lay], [fl for _, _, fl in lay])
+        assert rc == 0
+        sets.append([words[:, t].astype("<u4").tobytes().hex() for t in range(M.NPAIR)])
+    assert sets[0] == sets[1], "k_miller_wide2 and k_miller_wide differ in words"
+    return {"launches": [16, 257], "words": sets[0]}
+
+
 def write(name, obj):
     path = os.path.join(HERE, name)
     with open(path, "w") as f:
@@ -593,6 +619,8 @@ def main():
     def want(tag):
         return not which or tag in which
 
+    if "millerwide" in which:  # recorded from the device: by name only
+        write("miller_wide_words.json", make_miller_wide_words())
     if want("kat"):
         write("pairing_kat.json", make_pairing_kat(11))
     if want("keygen"):

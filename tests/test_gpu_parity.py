@@ -303,7 +303,7 @@ def test_ragged_batch_sizes_pair_lanes(ctxs, n):
 
 
 WIDE_MAX, FEXP_WIDE_MAX, PREP_WIDE_MAX = 4096, 2048, 1024  # slots.h kWideMax, kFexpWideMax, kPrepWideMax
-WIDE2_MAX_CREDS = 128  # fexp_pl.hip kWide2Max = 256 pairs: k_miller_wide2 (two waves a pair) up to 128 credentials
+WIDE2_MAX_CREDS = 128  # miller_wide.hip kWide2Max = 256 pairs: k_miller_wide2 (two waves a pair) up to 128 credentials
 
 
 @pytest.mark.parametrize("mode", ["G2", "G1"])
@@ -312,7 +312,7 @@ def test_small_batch_wide_miller_path_matches_pair_lane_path(ctxs, mode):
     k_wide_pairs -> k_miller_wide -> k_f12_reduce_wide), those of <= 2,048 also the one-wave-per-
     credential final exponentiation (kFexpWideMax: k_fexp1) and the one-wave prep; larger ones the
     pair-lane loop, the quad-lane fexp and the lane-pair prep; up to 128 credentials (256 pairs,
-    fexp_pl.hip kWide2Max) the wide loop runs two waves a pair (k_miller_wide2).  The same credentials (a
+    miller_wide.hip kWide2Max) the wide loop runs two waves a pair (k_miller_wide2).  The same credentials (a
     4,104 batch; its first 4,096, 2,049, 2,048, 1,025, 129, 128 and a ragged 37; then single credentials)
     give the same verdicts and GT bytes, with every corruption kind (identity sigmas included) in the
     batch."""

@@ -2,9 +2,9 @@
 """Instrumented op-count mirror of the HIP verify path (measurement infrastructure).
 
 Runs the SAME algorithm as the device code — the AMCL Fp2 -> Fp4 -> Fp12 tower of tower.inc, the
-line functions / sparse line multiply / Frobenius of pairing.inc, the shared-squaring 2-pair Miller
-loop of miller_pl.hip, the final-exponentiation chain of fexp_pl.hip and the fixed-base window MSM of
-kernels.hip — on Python integers, counting every Montgomery multiplication the kernels execute.
+line functions / sparse line multiply of pairing.inc, the Frobenius maps of tower_lz.h, the
+shared-squaring 2-pair Miller loop of miller_lz.hip, the final-exponentiation chain of fexp_q.hip /
+fexp_pl.hip and the fixed-base window MSM of kernels.hip — on Python integers, counting every Montgomery multiplication the kernels execute.
 Because it computes real values, tests/test_opcount.py checks its GT bytes against the golden
 fixtures: the counts belong to the algorithm that produces the reference's GT, not to a formula.
 
@@ -308,7 +308,7 @@ def eval_mul(f, l0, l2, l3, Pe):
 
 
 def miller2(pairs):
-    """miller_pl.hip: pairs = [(Q affine G2, P eval form, skip)]; shared squaring."""
+    """miller_lz.hip k_miller: pairs = [(Q affine G2, P eval form, skip)]; shared squaring."""
     Ts = [(q[0], q[1], F2_ONE) for q, _, _ in pairs]
     f = f12_one()
     for bit in range(62, -1, -1):
@@ -339,7 +339,7 @@ def _3u(u, v, plus):  # f2_3u_p2v / f2_3u_m2v: u + 2 (u +- v)
     return f2_add(f2_dbl(f2_add(u, v) if plus else f2_sub(u, v)), u)
 
 
-def cyc4_sqr(x):  # fexp_pl.hip cyc4_sqr: compressed cyclotomic squaring, six Fp2 squarings
+def cyc4_sqr(x):  # compressed cyclotomic squaring, six Fp2 squarings (fexp_q.hip qz_sqr, fexp_pl.hip cyc4_sqr_dist_lz)
     b0, b1, c0, c1 = x
     s0, s1 = f2_sqr(b0), f2_sqr(b1)
     Xb = f2_sub(f2_sub(f2_sqr(f2_add(b0, b1)), s0), s1)
@@ -350,7 +350,7 @@ def cyc4_sqr(x):  # fexp_pl.hip cyc4_sqr: compressed cyclotomic squaring, six Fp
     return (_3u(Xc, b0, True), _3u(Tc, b1, False), _3u(Tb, c0, False), _3u(Xb, c1, True))
 
 
-def cyc4_num(x):  # fexp_pl.hip cyc4_num
+def cyc4_num(x):  # the decompression's numerators and denominator (fexp_q.hip qz_num, fexp_pl.hip decompress3_wide)
     b0, b1, c0, c1 = x
     Nb = f2_sub(f2_sqr(b0), f2_xi(f2_sqr(b1)))
     Nc = f2_sub(f2_sqr(c0), f2_xi(f2_sqr(c1)))
@@ -393,7 +393,7 @@ def cyc_pow_x(y):  # fexp_pl.hip fx_pow_x: 57 compressed squarings, 3 decompress
     return f12_conj(acc)
 
 
-def final_exp(f):  # fexp_pl.hip k_fexp, step for step
+def final_exp(f):  # the chain of k_fexp_q / k_fexp1 (fexp_pl.hip fexp_chain), step for step
     t = f12_inv(f)
     f = f12_mul(f12_conj(f), t)
     f = f12_mul(f12_frob2(f), f)
@@ -566,7 +566,7 @@ def mul_aff(g, base, k):
 
 # ---------------------------------------------------------------- verify (SigG2 shared verkey, pair prep)
 def verify_sigg2(cred, vk_aff, gtil_aff, q):
-    """k_prep_sigg2_pair -> k_miller<2,false> -> k_fexp.  Returns (verdict, gt, {kernel: M})."""
+    """k_prep_sigg2_pair -> k_miller<2,false> -> k_fexp_q.  Returns (verdict, gt, {kernel: M})."""
     counts = {}
     s1 = decode(G2, bytes.fromhex(cred["sigma1"]))
     s2 = decode(G2, bytes.fromhex(cred["sigma2"]))
@@ -604,7 +604,7 @@ def _pair_sigg2(s1, s2, pr, gtil_aff, counts):
 
 
 def verify_sigg1(cred, vk_aff, gtil_aff, q):
-    """k_prep_sigg1<true> -> k_miller<1,false> (g~ lines precomputed) -> k_fexp."""
+    """k_prep_sigg1<true> -> k_miller<1,false> (g~ lines precomputed) -> k_fexp_q."""
     counts = {}
     s1 = decode(G1, bytes.fromhex(cred["sigma1"]))
     s2 = decode(G1, bytes.fromhex(cred["sigma2"]))
@@ -724,7 +724,7 @@ def straus(g, pts, scalars, to_affine=True):
 
 
 def verify_pervk(cred, gtil_aff, mode):
-    """pervk.hip k_prep_sig*_var (Straus over [Y~_1..q] with the messages, + X~) -> k_miller -> k_fexp.
+    """pervk.hip k_prep_sig*_var (Straus over [Y~_1..q] with the messages, + X~) -> k_miller -> k_fexp_q.
     Counted as ONE Straus over all q bases: the SigG2 kernel splits the bases over a lane pair and
     repeats the doubling chain on both lanes, which is not counted (the conservative figure)."""
     counts = {}
@@ -805,7 +805,7 @@ def enc(g, a):
 
 # ---------------------------------------------------------------- PoK verify (k_prep_pok, SigG2)
 def pok_sigg2(d, p, vk_aff, gtil):
-    """k_prep_pok<Fp2, Fp> -> k_miller<2,false> -> k_fexp."""
+    """k_prep_pok<Fp2, Fp> -> k_miller<2,false> -> k_fexp_q."""
     counts = {}
     q, rev = d["q"], d["revealed"]
     X, Ys = vk_aff
@@ -857,7 +857,7 @@ def pok_sigg2(d, p, vk_aff, gtil):
 
 
 def pok_sigg1(d, p, vk_aff, gtil):
-    """k_prep_pok_g1pl (SigG1: the Schnorr MSM and J' in G2 on lane pairs) -> k_miller<1,false> -> k_fexp."""
+    """k_prep_pok_g1pl (SigG1: the Schnorr MSM and J' in G2 on lane pairs) -> k_miller<1,false> -> k_fexp_q."""
     counts = {}
     q, rev = d["q"], d["revealed"]
     X, Ys = vk_aff
@@ -928,7 +928,7 @@ RLC_N, RLC_PSEUDO = 131072, 16  # credentials per GPU (config 3), fold pseudo-cr
 def rlc_sigg2(cred, vk_aff, gtil_aff, q, rnd):
     """k_rlc_check_sigg2 + k_rlc_msm_sigg2 -> fold (fold.hip) -> k_miller4<2> (four
     credentials' first pairs per shared-squaring loop) -> the product tree over RLC_N / 4 values; the
-    finish's 16 window pairs (one-pair loops, fexp_pl.hip k_miller_wide) and the batch's one final
+    finish's 16 window pairs (one-pair loops, miller_wide.hip k_miller_wide) and the batch's one final
     exponentiation are outside the partial's phases (amortised over RLC_N they are < 0.1 %).
     delta is a random 128-bit value here (the counts do not depend on the key stream)."""
     counts = {}
