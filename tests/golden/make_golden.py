@@ -606,6 +606,37 @@ def make_miller_wide_words():
     return {"launches": [16, 257], "words": sets[0]}
 
 
+def make_miller_lz_words():
+    """The pair-lane Miller loops' own output words (csrc/miller_lz.hip) for the first 8 elements of the
+    plain block of tests/miller_lz_cases.py, per launcher: two-pair SigG2 and SigG1, twin, quad.  Recorded
+    from the device like miller_wide_words.json, so made only when asked for by name
+
+        python tests/golden/make_golden.py millerlz
+
+    Each launch first passes the GT comparison with the C oracle (test_gpu_miller_lz_direct
+    check_against_oracle); the words must agree between the two largest sizes (the first block full, and
+    one element into the second), and between the SigG2 and SigG1 builds of the twin and quad loops, which
+    are stored once.  144 little-endian words in hex per element."""
+    root = os.path.dirname(os.path.dirname(HERE))
+    sys.path[:0] = [os.path.join(root, "tests"), os.path.join(root, "coconut-rust_amd")]
+    import miller_lz_cases as M
+    import test_gpu_miller_lz_direct as T
+    from conftest import oracle_lib
+    K, oc = T.launchers(), oracle_lib()
+    rec, sizes = {}, {}
+    for lid in T.LAUNCHERS:
+        kind = T.KIND[lid]
+        sets = []
+        for n in M.SIZES[kind][-2:]:
+            words = T.check_against_oracle(K, oc, lid, n)
+            sets.append([words[:, e].astype("<u4").tobytes().hex() for e in range(T.RECORDED)])
+        assert sets[0] == sets[1], f"{lid}: the words depend on the launch size"
+        key = T.recorded_key(lid)
+        assert rec.setdefault(key, sets[0]) == sets[0], f"{key}: the SigG2 and SigG1 builds differ in words"
+        sizes[key] = list(M.SIZES[kind][-2:])
+    return {"launches": sizes, "words": rec}
+
+
 def write(name, obj):
     path = os.path.join(HERE, name)
     with open(path, "w") as f:
@@ -621,6 +652,8 @@ def main():
 
     if "millerwide" in which:  # recorded from the device: by name only
         write("miller_wide_words.json", make_miller_wide_words())
+    if "millerlz" in which:
+        write("miller_lz_words.json", make_miller_lz_words())
     if want("kat"):
         write("pairing_kat.json", make_pairing_kat(11))
     if want("keygen"):
