@@ -72,8 +72,10 @@ DEV Fq<AN, BC> ld_Pc(const PSrc& s, int slot, size_t i) {
 // e(P, O) = 1) multiplies by the unit line (1, 0, 0) instead of returning early: the product's type
 // bound then holds on every path (f's value bound only shrinks through a multiplication), and the
 // lanes of a mixed wave would wait for the others anyway.
+// first (wave-uniform): f is the unit, as at the loop's first line; the product is then the line itself,
+// A + C w^2 with A = (l0, l3), C = (l2, 0), or the unit for a skipped pair: no Fp2 product.
 template <int B>
-DEV F12S eval_mul(const F12<AS, B>& f, const LineS& ln, const PSrc& ps, size_t i, bool skip) {
+DEV F12S eval_mul(const F12<AS, B>& f, const LineS& ln, const PSrc& ps, size_t i, bool skip, bool first = false) {
     constexpr int32_t ONE_R[LN] = {LZ_C_OUT_LIMBS};
     using A0 = decltype(mul_fpr(ln.l0, fq_const(ONE_R)));
     A0 a0;
@@ -83,8 +85,10 @@ DEV F12S eval_mul(const F12<AS, B>& f, const LineS& ln, const PSrc& ps, size_t i
     const auto a3 = mul_fpr(ln.l3, ld_Pc(ps, 1, i));
     using L = decltype(a0);
     const L one = fit<AN, L::BV>(f2_one()), zero = fit<AN, L::BV>(f2_zero());
-    return fit<AS, BF>(f12_mul_line(f, L{sel(skip, one.c, a0.c)}, L{sel(skip, zero.c, fit<AN, L::BV>(a2).c)},
-                                    L{sel(skip, zero.c, fit<AN, L::BV>(a3).c)}));
+    const L e0{sel(skip, one.c, a0.c)}, e2{sel(skip, zero.c, fit<AN, L::BV>(a2).c)},
+        e3{sel(skip, zero.c, fit<AN, L::BV>(a3).c)};
+    if (first) return fit<AS, BF>(mk12(mk4(e0, e3), mk4(zero, zero), mk4(e2, zero)));
+    return fit<AS, BF>(f12_mul_line(f, e0, e2, e3));
 }
 
 // Two-pair loop: both twist points are parked in LDS while f is multiplied by their lines (the values
@@ -245,7 +249,8 @@ __global__ __launch_bounds__(MB, 2) void k_miller(size_t n, size_t ps, const uin
                 ln = fit_line(line_dbl(T));
                 park(lds, k, T);
             }
-            g = fit<AS, BS>(eval_mul(g, ln, k ? ps1 : ps0, i, k ? skip1 : skip0));
+            // b = 62: f = 1, so the first pair's line starts g
+            g = fit<AS, BS>(eval_mul(g, ln, k ? ps1 : ps0, i, k ? skip1 : skip0, b == 62 && k == 0));
         }
         // both passes ran, so g holds an eval_mul result, whose type bound is BF
         f = narrow_to<BF>(g);

@@ -257,6 +257,7 @@ struct G2P {
 // projective):  B = Y^2, C = Z^2, E = 3 b' C = 12 xi C, F = 3E, H = (Y + Z)^2 - B - C,
 //   X' = 2 XY (B - F),  Y' = (B + F)^2 - 12 E^2,  Z' = 4 B H;
 // line before evaluation at P: l0 = E - B, l2c = 3 X^2, l3c = -H.
+// 2 XY = (X + Y)^2 - X^2 - B: a squaring in place of a product (X^2 and B are computed anyway).
 template <class L0, class L2, class L3>
 struct Line {
     L0 l0;
@@ -268,16 +269,17 @@ DEV Line<L0, L2, L3> mk_line(const L0& l0, const L2& l2, const L3& l3) { return 
 
 template <int BX, int BY, int BZ>
 DEV auto line_dbl(G2P<BX, BY, BZ>& T) {
-    const auto a = mulr(T.x, T.y);
     const auto b = sqrr(T.y);
     const auto c = sqrr(T.z);
+    const auto x2 = sqrr(T.x);
+    const auto a2 = sub(sub(sqrr(add(T.x, T.y)), x2), b);  // 2 XY from a squaring: X^2 and Y^2 are there
     const auto e3 = norm(smul<3>(xi(c)));             // 3 xi C
     const auto e = smul<4>(e3);                        // E = 12 xi C
     const auto f = dbl(norm(smul<6>(e3)));            // F = 3 E = 2 (6 e3)
-    const auto ln = mk_line(norm(sub(e, b)), norm(smul<3>(sqrr(T.x))), norm(neg(sub(sub(sqrr(add(T.y, T.z)), b), c))));
+    const auto ln = mk_line(norm(sub(e, b)), norm(smul<3>(x2)), norm(neg(sub(sub(sqrr(add(T.y, T.z)), b), c))));
     const auto h = neg(ln.l3);                         // H (squeezed)
     const auto t = sqrr(norm(e));
-    T.x = fit<AS, BX>(norm(dbl(mulr(a, sub(b, f)))));
+    T.x = fit<AS, BX>(norm(mulr(a2, sub(b, f))));
     T.y = fit<AS, BY>(norm(sub(sqrr(add(b, f)), smul<3>(norm(smul<4>(t))))));
     T.z = fit<AS, BZ>(norm(smul<4>(mulr(b, h))));
     return ln;
