@@ -15,7 +15,7 @@
 //   void* alloc(size_t)   nullptr on failure          void free(void*)
 //   int h2d(void* d, const void* h, size_t, Stream)   int d2h(void* h, const void* d, size_t, Stream)
 //   int zero(void* d, size_t, Stream)                 int sync(Stream)               (0: ok)
-// capi.cpp instantiates both over hipMalloc / hipMemcpyAsync (HipMem); tests/host/test_devbuf.cpp
+// ctx.h instantiates both over hipMalloc / hipMemcpyAsync (HipMem); tests/host/test_devbuf.cpp
 // over a simulated device that logs every operation and can fail the k-th one, built with
 // -fsanitize=address,undefined (tests/test_sanitizers.py).
 #pragma once

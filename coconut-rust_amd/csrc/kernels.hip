@@ -382,7 +382,7 @@ __global__ __launch_bounds__(256, 2) void k_prep_sigg1_pair(size_t n, int q, con
     if (!h) flags[i] = fl;
 }
 
-// Small batches (capi.cpp: n <= kWideMax): ONE WAVE per credential, its verkey MSM's window terms
+// Small batches (capi_verify.cpp: n <= kWideMax): ONE WAVE per credential, its verkey MSM's window terms
 // spread over the lanes.  The pair kernels above walk all q x nwin terms on one lane (pair) — the whole
 // launch then lasts one such chain, however few credentials there are.  Here term t = (j, w) goes to
 // lane (pair) t mod 64 (32), lane (pair) 0 also takes X~, and a butterfly sums the partial sums

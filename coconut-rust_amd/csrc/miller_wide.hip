@@ -2,7 +2,7 @@
 // tower_wide.h — the 32 lane pairs hold the same values and a step's independent Fp2 products are spread
 // over them.  Two kernels walk the same chain: k_miller_wide (one wave a pair) and k_miller_wide2 (two
 // waves a pair, for launches smaller than the chip).  Users: the RLC fold's 16 window pairs (fold.hip)
-// and small batches (capi.cpp: n <= kWideMax, laid out by k_wide_pairs below).
+// and small batches (capi_verify.cpp: n <= kWideMax, laid out by k_wide_pairs below).
 //
 // CC_FP_INLINE: the Fp multiplications are inlined (Makefile HOT_INLINE=1), as in fexp_pl.hip.
 #ifdef CC_HOT_INLINE  // build option (Makefile HOT_INLINE=1): inline every Fp multiplication
@@ -360,7 +360,7 @@ __global__ __launch_bounds__(128, 1) void k_miller_wide2(size_t n, const uint32_
 // ================================================================ small batches: one wave per pair
 // A batch of n credentials fills 2n lanes of the batch Miller kernel (miller_lz.hip k_miller): for small
 // n that is a handful of waves, each the latency of a 2-pair loop on one lane pair (~7.5 ms alone on its
-// SIMD, whatever n up to ~4k).  For n <= kWideMax (capi.cpp) each credential's two pairs run instead as
+// SIMD, whatever n up to ~4k).  For n <= kWideMax (capi_verify.cpp) each credential's two pairs run instead as
 // two waves of k_miller_wide (~1.8 ms), and k_f12_reduce_wide (fexp_pl.hip) multiplies each credential's
 // two Miller values.  k_wide_pairs lays the pairs out for it: pair 2i = credential i's pair 0, 2i + 1 its
 // pair 1, Q affine (storage R form) in slots S_Q1.., P in evaluation form (X Z, Y, Z^3) in S_P1..; wide

@@ -131,7 +131,7 @@ __global__ __launch_bounds__(256, 2) void k_prep_sigg1_var(size_t n, int q, cons
     if (!h) flags[i] = fl;
 }
 
-// Small batches (capi.cpp kFexpWideMax): ONE WAVE per credential.  A Straus chain's 260 doublings are
+// Small batches (capi_verify.cpp kFexpWideMax): ONE WAVE per credential.  A Straus chain's 260 doublings are
 // the same for one base as for q, so the wave's lanes are split into GROUPS of 4 lanes (G1) or 4 lane
 // pairs (G2), group g takes the bases k = g, g + NG, ..., and each group runs its chain with the
 // products of every doubling and addition spread over its members (curve_wide_lz.h): 3 product times a

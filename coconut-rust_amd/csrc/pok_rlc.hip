@@ -14,7 +14,7 @@
 // relation holds and the delta-weighted product is one; a forged batch passes with probability
 // <= 2^-127.  Part 0 of the partial is rlc.hip's k_rlc_check_* on (sigma'_1, sigma'_2) unchanged; the
 // kernels here are its part 1; the fold, the Miller loop (two proofs a loop while those waves fit one a
-// SIMD, capi.cpp pok_rlc_twin; four beyond) and the product tree follow as for signatures.
+// SIMD, capi_pok.cpp pok_rlc_twin; four beyond) and the product tree follow as for signatures.
 //
 //   k_rlc_pok_sigg2 / k_rlc_pok_sigg1 : the Schnorr check (flag bit 3), J's subgroup test (flag bit 6)
 //                                       and delta J' = delta X~ + sum_revealed (delta m) Y~ + delta J as

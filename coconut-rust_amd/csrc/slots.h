@@ -1,5 +1,5 @@
 // Host-only bookkeeping of a context's verify workspaces and of its concurrency slots
-// (cc_set_concurrency, capi.cpp): the bytes a batch of n credentials needs in each workspace, the
+// (cc_set_concurrency, capi_ctx.cpp): the bytes a batch of n credentials needs in each workspace, the
 // workspace set one launch reads (every member named), the round-robin choice of a slot, and the
 // protocol that keeps a slot's buffers alive while its last batch may still read them:
 //
@@ -9,13 +9,16 @@
 //   end    records the slot's `done` on the launch stream;
 //   Fence  (RAII) ends a begun slot on every exit, so a launch that fails half-way still fences the
 //          kernels it queued (the next user of the slot waits for them before growing the buffers).
+// Staging is a slot's pinned upload ring.
 //
-// No HIP types here: the device is a policy class.  capi.cpp instantiates it over hipMalloc'd buffers
-// and hipEvent_t (HipDev); tests/host/test_slots.cpp over a simulated device timeline that flags a
-// buffer reallocated while a queued operation still reads it, built with -fsanitize=address,undefined
-// (tests/test_sanitizers.py, `pytest -m "not gpu"`).
+// No HIP types here: the device is a policy class.  ctx.h instantiates it over hipMalloc'd buffers,
+// hipEvent_t and hipHostMalloc (HipDev); tests/host/test_slots.cpp over a simulated device timeline that
+// flags a buffer reallocated while a queued operation still reads it and copies from a staging entry only
+// when its stream runs, built with -fsanitize=address,undefined (tests/test_sanitizers.py,
+// `pytest -m "not gpu"`).
 #pragma once
 #include <stddef.h>
+#include <string.h>
 
 #include <vector>
 
@@ -23,7 +26,7 @@ namespace cc {
 namespace slots {
 
 constexpr size_t kPrepSlots = 14;  // Fp slots of the prep SoA (soa.h)
-// Small batches run the one-wave kernels (capi.cpp launch_miller / launch_verify): the Miller loop one
+// Small batches run the one-wave kernels (capi_verify.cpp launch_miller / launch_verify): the Miller loop one
 // wave per pair up to kWideMax credentials (its own prep / flags / Miller-value workspaces), the final
 // exponentiation one wave per credential up to kFexpWideMax (its chain in the scratch), the PoK and
 // per-credential-verkey preps one wave per credential up to kPrepWideMax.
@@ -96,11 +99,6 @@ struct SlotBufs {
     Buf prep, flags, fbuf, vkb, scratch, idx, wprep, wflags, wf;
     Buf rkey, rany, rpts, rdig, rwork;
     Work<Buf> work() { return Work<Buf>(&prep, &flags, &fbuf, &vkb, &scratch, &idx, &wprep, &wflags, &wf); }
-    template <class F>
-    void each(F f) {
-        for (Buf* b : {&prep, &flags, &fbuf, &vkb, &scratch, &idx, &wprep, &wflags, &wf, &rkey, &rany, &rpts, &rdig, &rwork})
-            f(*b);
-    }
 };
 
 // The slots of one context.  Dev provides Buf (with .bytes), Event, Stream and
@@ -121,7 +119,6 @@ struct Pool {
     std::vector<Rec> recs;  // recs[0]: the context's own workspaces
     int next = 0;
 
-    int size() const { return (int)recs.size(); }
     // the next slot, round-robin
     int take() {
         const int k = next;
@@ -183,6 +180,58 @@ struct Fence {
     }
     Fence(const Fence&) = delete;
     Fence& operator=(const Fence&) = delete;
+};
+
+// Pinned host staging for the few bytes a slot's batch uploads per call (the RLC delta seed, the PoK
+// revealed indices): a copy from pageable memory may hold the host until the stream reaches it, i.e.
+// until the slot's previous batch has run, which would serialize the in-flight batches.  A ring of kR
+// entries, each reused only after its own copy (kR calls earlier on this slot) has completed.  Beside
+// Pool's sync and record, Dev provides
+//   void* pin(size_t)  pinned host block, nullptr on failure     void unpin(void*)
+//   int create(Event&)                                           void destroy(Event)
+//   int h2d(void* d, const void* h, size_t, Stream)              the queued host-to-device copy
+template <class Dev>
+struct Staging {
+    static constexpr int kR = 4;
+    unsigned char* host = nullptr;
+    size_t bytes = 0;  // per entry
+    typename Dev::Event ev[kR] = {};
+    bool used[kR] = {};
+    int next = 0;
+    // copies len bytes of src to d_dst on st through the next entry
+    int upload(Dev& d, void* d_dst, const void* src, size_t len, typename Dev::Stream st) {
+        if (!len) return 0;
+        if (len > bytes) {
+            for (int e = 0; e < kR; e++)
+                if (used[e] && d.sync(ev[e])) return -1;
+            if (host) d.unpin(host);
+            host = nullptr, bytes = 0;
+            const size_t want = (len + 63) & ~(size_t)63;
+            if (!(host = (unsigned char*)d.pin(want * kR))) return -1;
+            bytes = want;
+            for (int e = 0; e < kR; e++) used[e] = false;
+        }
+        const int e = next;
+        next = (next + 1) % kR;
+        if (!ev[e] && d.create(ev[e])) return -1;
+        if (used[e] && d.sync(ev[e])) return -1;  // its copy kR calls ago
+        unsigned char* h = host + (size_t)e * bytes;
+        memcpy(h, src, len);
+        if (d.h2d(d_dst, h, len, st)) return -1;
+        if (d.record(ev[e], st)) return -1;
+        used[e] = true;
+        return 0;
+    }
+    void release(Dev& d) {
+        for (int e = 0; e < kR; e++) {
+            if (used[e]) (void)d.sync(ev[e]);
+            if (ev[e]) d.destroy(ev[e]);
+            ev[e] = {};
+            used[e] = false;
+        }
+        if (host) d.unpin(host);
+        host = nullptr, bytes = 0;
+    }
 };
 
 }  // namespace slots

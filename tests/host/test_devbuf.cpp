@@ -1,5 +1,5 @@
 // Host-only test of the owned device buffers and of the host forms' sequence
-// (coconut-rust_amd/csrc/devbuf.h) that capi.cpp runs over HIP.  Here the device is simulated:
+// (coconut-rust_amd/csrc/devbuf.h) that the capi_*.cpp files run over HIP.  Here the device is simulated:
 // an allocation is a host block with a guard before and a canary after it, every device operation is
 // appended to a log, and the k-th operation of one kind can be made to fail.  Built with
 // -fsanitize=address,undefined by tests/test_sanitizers.py (LeakSanitizer on); exits non-zero on the

@@ -1,12 +1,16 @@
-// Host-only test of the concurrency-slot bookkeeping (coconut-rust_amd/csrc/slots.h) that capi.cpp
-// runs over HIP.  Here the device is simulated: every stream is a FIFO of queued operations, an event
-// marks a stream position, a "kernel" reads a set of buffers (id + allocation generation), and a buffer
-// reallocated while a queued operation still reads its old allocation is counted as a use-after-free
-// (what the GPU would do with a hipFree'd workspace).  Built with -fsanitize=address,undefined by
-// tests/test_sanitizers.py; exits non-zero on the first failed check.
+// Host-only test of the concurrency-slot bookkeeping (coconut-rust_amd/csrc/slots.h) that the capi_*.cpp
+// files run over HIP (csrc/ctx.h HipDev).  Here the device is simulated: every stream is a FIFO of queued
+// operations, an event marks a stream position, a "kernel" reads a set of buffers (id + allocation
+// generation), and a buffer reallocated while a queued operation still reads its old allocation is counted
+// as a use-after-free (what the GPU would do with a hipFree'd workspace).  A queued copy of the pinned
+// upload ring (Staging) reads its source only when its stream runs, and the pinned blocks are heap blocks:
+// an entry reused too early shows as wrong bytes, a block freed too early as an AddressSanitizer report.
+// Built with -fsanitize=address,undefined by tests/test_sanitizers.py; exits non-zero on a failed check.
 #include <stdio.h>
 #include <stdlib.h>
+#include <string.h>
 
+#include <algorithm>
 #include <deque>
 #include <map>
 #include <vector>
@@ -39,6 +43,9 @@ struct FakeDev {
         std::vector<std::pair<int, int>> reads;  // (buffer id, generation)
         int wait_stream = -1;                    // a wait: completes after that stream reaches wait_seq
         long wait_seq = -1;
+        void* dst = nullptr;  // a copy: n bytes of src to dst when the operation runs
+        const void* src = nullptr;
+        size_t n = 0;
     };
     std::vector<std::deque<Op>> streams;
     std::map<int, std::pair<int, long>> evs;  // event -> (stream, seq of its last op when recorded)
@@ -69,6 +76,7 @@ struct FakeDev {
         return 0;
     }
     int record(Event e, Stream s) {
+        if (hit()) return failed_record = true, -1;
         if (!e) return -1;
         evs[e] = {s, streams[(size_t)s].empty() ? -1 : streams[(size_t)s].back().seq};
         return 0;
@@ -84,9 +92,38 @@ struct FakeDev {
         return 0;
     }
     int sync(Event e) {
+        if (hit()) return -1;
         auto it = evs.find(e);
         if (it == evs.end()) return 0;
         run_until(it->second.first, it->second.second);
+        return 0;
+    }
+    // --- and Staging: the calls are counted and the fail_at-th fails (Pool's tests never set it)
+    int calls = 0, fail_at = -1, live_events = 0, live_pins = 0;
+    bool failed_record = false;
+    bool hit() { return calls++ == fail_at; }
+    void* pin(size_t n) {
+        if (hit()) return nullptr;
+        live_pins++;
+        return malloc(n);
+    }
+    void unpin(void* p) {
+        live_pins--;
+        free(p);
+    }
+    int create(Event& e) {
+        if (hit()) return -1;
+        live_events++;
+        e = new_event();
+        return 0;
+    }
+    void destroy(Event) { live_events--; }
+    int h2d(void* d, const void* h, size_t n, Stream s) {
+        if (hit()) return -1;
+        Op o;
+        o.seq = ++seq;
+        o.dst = d, o.src = h, o.n = n;
+        streams[(size_t)s].push_back(o);
         return 0;
     }
     // --- the simulated device
@@ -96,6 +133,7 @@ struct FakeDev {
         while (!q.empty() && q.front().seq <= upto) {
             Op o = q.front();
             if (o.wait_stream >= 0) run_until(o.wait_stream, o.wait_seq);
+            if (o.n) memcpy(o.dst, o.src, o.n);
             q.pop_front();
         }
     }
@@ -118,7 +156,7 @@ struct FakeDev {
     }
 };
 
-// a context's slot 0 (its own workspaces) + K-1 slot buffer sets, as capi.cpp cc_set_concurrency builds
+// a context's slot 0 (its own workspaces) + K-1 slot buffer sets, as capi_ctx.cpp cc_set_concurrency builds
 struct Ctx {
     FakeDev dev;
     Pool<FakeDev> pool;
@@ -140,7 +178,7 @@ struct Ctx {
     ~Ctx() {
         for (auto* e : extra) delete e;
     }
-    // one verify batch as capi.cpp verify_device runs it on a slot; fail_after: the launch "fails" after
+    // one verify batch as capi_verify.cpp verify_device runs it on a slot; fail_after: the launch "fails" after
     // queueing that many kernels (the Fence must still end the slot)
     int batch(int stream, size_t n, size_t vkw = 0, int fail_after = -1, bool use_fence = true) {
         const Sizes sz = verify_sizes(n, vkw, 0, 0);
@@ -259,7 +297,144 @@ static void test_drain() {
     CHECK(!c.dev.read_pending(c.own.prep.id, c.own.prep.gen));
 }
 
+// ---------------------------------------------------------------- the pinned upload ring (Staging)
+// a device whose event synchronise does nothing: what the ring would be without its waits
+struct NoSyncDev : FakeDev {
+    using FakeDev::FakeDev;
+    int sync(Event) { return 0; }
+};
+
+// one ring on stream 1 of a two-stream device, which runs only when the ring (or the test) makes it
+template <class Dev>
+struct Ring {
+    static constexpr int kR = Staging<Dev>::kR;
+    Dev dev{2};
+    Staging<Dev> g;
+    std::deque<std::vector<unsigned char>> want, dst;
+    std::vector<bool> ok;
+    // the next upload, of distinct contents; the caller's array is scribbled over as soon as the call returns
+    int up(size_t len) {
+        const int i = (int)want.size();
+        want.emplace_back(len);
+        for (size_t j = 0; j < len; j++) want.back()[j] = (unsigned char)(37 * i + (int)j + 1);
+        dst.emplace_back(len, (unsigned char)0);
+        std::vector<unsigned char> tmp = want.back();
+        const int rc = g.upload(dev, len ? dst.back().data() : nullptr, len ? tmp.data() : nullptr, len, 1);
+        std::fill(tmp.begin(), tmp.end(), (unsigned char)0xEE);
+        ok.push_back(rc == 0);
+        return rc;
+    }
+    // destinations of successful uploads that do not hold their own bytes
+    int wrong() const {
+        int w = 0;
+        for (size_t i = 0; i < want.size(); i++) w += ok[i] && dst[i] != want[i];
+        return w;
+    }
+    bool pending() const { return !dev.streams[1].empty(); }
+    bool all_released() const { return !g.host && !g.bytes && !dev.live_pins && !dev.live_events; }
+};
+
+// case 1: kR + 3 uploads on a stream that runs only at the end; returns the wrong destinations
+template <class Dev>
+static int ring_reuse_wrong() {
+    Ring<Dev> r;
+    for (int i = 0; i < Ring<Dev>::kR + 3; i++) CHECK(r.up(24) == 0);
+    CHECK(r.g.bytes == 64);  // rounded up to 64 bytes an entry
+    CHECK(r.pending());      // the last kR copies are still queued
+    r.dev.run_all();
+    const int w = r.wrong();
+    r.g.release(r.dev);
+    CHECK(r.all_released());
+    return w;
+}
+
+static void test_ring_reuse_waits_for_its_entry() {
+    CHECK(ring_reuse_wrong<FakeDev>() == 0);
+    // teeth: without the wait an entry is overwritten while its copy is queued
+    CHECK(ring_reuse_wrong<NoSyncDev>() > 0);
+}
+
+// case 2: a larger upload arrives while earlier copies are queued: they run before their block is freed
+static void test_ring_growth_waits_for_every_entry() {
+    Ring<FakeDev> r;
+    for (int i = 0; i < 3; i++) CHECK(r.up(16) == 0);
+    CHECK(r.pending() && r.g.bytes == 64);
+    CHECK(r.up(200) == 0);
+    CHECK(r.g.bytes == 256 && r.dev.live_pins == 1);
+    for (int i = 0; i < 3; i++) CHECK(r.dst[(size_t)i] == r.want[(size_t)i]);  // ran before the free
+    CHECK(r.pending());  // the large one is queued
+    for (int i = 0; i < Ring<FakeDev>::kR + 1; i++) CHECK(r.up(i % 2 ? 200 : 16) == 0);
+    r.dev.run_all();
+    CHECK(r.wrong() == 0);
+    r.g.release(r.dev);
+    CHECK(r.all_released());
+}
+
+// case 3: a zero-length upload makes no device call, takes no entry and touches neither pointer
+static void test_ring_zero_length() {
+    Ring<FakeDev> r;
+    CHECK(r.up(0) == 0 && r.dev.calls == 0 && !r.g.host);
+    CHECK(r.up(16) == 0);
+    const int calls = r.dev.calls, next = r.g.next;
+    CHECK(r.up(0) == 0 && r.dev.calls == calls && r.g.next == next);
+    CHECK(r.up(16) == 0);
+    r.dev.run_all();
+    CHECK(r.wrong() == 0);
+    r.g.release(r.dev);
+    CHECK(r.all_released());
+}
+
+// case 4: every device call of a run with reuse and growth fails in turn: that upload reports it, the next
+// upload and release are clean.  (A failed record leaves its copy queued with no event to wait for; the
+// caller's stream is past use then, and the test lets it run before it goes on.)
+static void test_ring_failures() {
+    const size_t lens[] = {16, 16, 16, 16, 16, 16, 200, 16};
+    int ncalls = 0;
+    for (int k = -1; k < ncalls || k < 0; k++) {
+        Ring<FakeDev> r;
+        r.dev.fail_at = k;
+        int failed = 0;
+        for (size_t len : lens)
+            if (r.up(len)) {
+                failed++;
+                break;
+            }
+        if (k < 0) {
+            ncalls = r.dev.calls;
+            CHECK(failed == 0 && ncalls > 20);
+        } else {
+            CHECK(failed == 1);
+        }
+        r.dev.fail_at = -1;
+        if (r.dev.failed_record) r.dev.run_all();
+        CHECK(r.up(48) == 0);
+        r.dev.run_all();
+        CHECK(r.wrong() == 0 && r.dst.back() == r.want.back());
+        r.g.release(r.dev);
+        CHECK(r.all_released());
+    }
+}
+
+// case 5: release with copies queued waits for them before the block goes; the ring is usable again
+static void test_ring_release_pending() {
+    Ring<FakeDev> r;
+    for (int i = 0; i < 3; i++) CHECK(r.up(32) == 0);
+    CHECK(r.pending());
+    r.g.release(r.dev);
+    CHECK(r.all_released() && r.wrong() == 0);
+    CHECK(r.up(32) == 0);
+    r.dev.run_all();
+    CHECK(r.wrong() == 0);
+    r.g.release(r.dev);
+    CHECK(r.all_released());
+}
+
 int main() {
+    test_ring_reuse_waits_for_its_entry();
+    test_ring_growth_waits_for_every_entry();
+    test_ring_zero_length();
+    test_ring_failures();
+    test_ring_release_pending();
     test_sizes();
     test_work_complete();
     test_round_robin();

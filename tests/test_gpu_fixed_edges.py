@@ -13,7 +13,7 @@ tests/fixed_edges.py, whose branch coverage tests/test_fixed_edges_model.py asse
   takes g~'s term alone: the boundary between the roles never falls inside the hidden responses here);
 * cc_fixed_base_mul (8-bit storage-form tables) for edge scalars over the generator, a random point, the
   identity and an off-curve encoding, both groups, against oc_msm;
-* the pinned staging ring of a concurrency slot (capi.cpp Staging): more cc_pok_verify_batch_device calls
+* the pinned staging ring of a concurrency slot (slots.h Staging): more cc_pok_verify_batch_device calls
   per slot than the ring has entries, each with its own revealed-index set, one of them large enough to
   regrow the ring.
 """

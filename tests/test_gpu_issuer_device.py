@@ -1,4 +1,4 @@
-"""GPU tests of the issuer's device forms (csrc/issue_dev.hip, capi.cpp): cc_sigreq_verify_batch_device and
+"""GPU tests of the issuer's device forms (csrc/issue_dev.hip, capi_issuer.cpp): cc_sigreq_verify_batch_device and
 cc_blind_sign_batch_device against the host forms they mirror, the C oracle and the intended verdicts, in
 both group modes, on caller streams.  Inputs: tests/issuer_edges.py (every call of the host form's edge
 suite) and tests/issuer_device_cases.py (the exceptional steps of the device form's own window schedule;

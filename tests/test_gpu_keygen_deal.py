@@ -1,4 +1,4 @@
-"""GPU tests of the keygen entry points (csrc/keygen.hip, capi.cpp): cc_set_keygen_params,
+"""GPU tests of the keygen entry points (csrc/keygen.hip, capi_keygen.cpp): cc_set_keygen_params,
 cc_keygen_deal_batch(_device) and cc_keygen_combine_batch(_device), byte for byte against the oracle's
 pedersen_deal / get_shared_secret and the restatement in tests/keygen_deal_cases.py (whose cases
 tests/test_keygen_deal_model.py checks on the CPU), in both group modes, with forced 8-bit tables unless a test

@@ -308,7 +308,7 @@ WIDE2_MAX_CREDS = 128  # miller_wide.hip kWide2Max = 256 pairs: k_miller_wide2 (
 
 @pytest.mark.parametrize("mode", ["G2", "G1"])
 def test_small_batch_wide_miller_path_matches_pair_lane_path(ctxs, mode):
-    """Batches of <= 4,096 credentials take the one-wave-per-pair Miller path (capi.cpp kWideMax:
+    """Batches of <= 4,096 credentials take the one-wave-per-pair Miller path (slots.h kWideMax:
     k_wide_pairs -> k_miller_wide -> k_f12_reduce_wide), those of <= 2,048 also the one-wave-per-
     credential final exponentiation (kFexpWideMax: k_fexp1) and the one-wave prep; larger ones the
     pair-lane loop, the quad-lane fexp and the lane-pair prep; up to 128 credentials (256 pairs,

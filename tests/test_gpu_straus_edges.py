@@ -5,7 +5,7 @@ comparison is byte equality with the C oracle.
 * Signature::verify with a verkey per credential, q = 3 and q = 18 (more than 16 and than 8: lane groups of
   the one-wave prep hold two bases), both modes: every case as a valid credential and as its twin with
   sigma_2 off by G (whose GT bytes pin the MSM's point), as one small batch (k_prep_sig*_var_wide), as single
-  credentials, and tiled by repetition just past kPrepWideMax (capi.cpp: the per-verkey prep becomes
+  credentials, and tiled by repetition just past kPrepWideMax (capi_verify.cpp: the per-verkey prep becomes
   k_prep_sigg2_var / k_prep_sigg1_var), kFexpWideMax and kWideMax (the batch Miller loop);
 * Signature::aggregate for t in {1, 2, 3, 5, 17, 33} with t + 1 entries a row (the unused one present),
   <= 64 rows a call, Lagrange scalars 2 and r - 1 among them; an all-identity row gives the identity;

@@ -40,7 +40,7 @@ pytestmark = pytest.mark.gpu
 
 MODES = {"G2": 0, "G1": 1}
 WIDE_MAX, FEXP_WIDE_MAX = 4096, 2048  # slots.h kWideMax, kFexpWideMax
-# <= 128 credentials: k_miller_wide2 (capi.cpp: kWide2Max = 256 pairs); <= kFexpWideMax: k_fexp1, above it the
+# <= 128 credentials: k_miller_wide2 (miller_wide.hip: kWide2Max = 256 pairs); <= kFexpWideMax: k_fexp1, above it the
 # quad-lane final exponentiation; above kWideMax the pair-lane k_miller
 SIZES = (16, 136, FEXP_WIDE_MAX + 8, WIDE_MAX + 8)
 FX = T.fixture()

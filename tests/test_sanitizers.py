@@ -4,10 +4,11 @@
   oracle's golden-fixture tests (tests/test_oracle.py) and the multi-rank gloo tests (tests/test_dist.py,
   whose CPU engine takes its verdicts from the oracle) — in a child pytest with CC_ORACLE_SAN=1, so no
   sanitizer runtime is loaded into this process.
-* The concurrency-slot bookkeeping of the C ABI (coconut-rust_amd/csrc/slots.h, the code capi.cpp runs over
-  HIP streams and events) is compiled with the same sanitizers against a simulated device timeline
+* The concurrency-slot bookkeeping of the C ABI (coconut-rust_amd/csrc/slots.h, the code the capi_*.cpp files
+  run over HIP streams and events) is compiled with the same sanitizers against a simulated device timeline
   (tests/host/test_slots.cpp): a workspace set missing a member must be refused, a slot's buffers must not
-  be reallocated while its batch is queued, and a launch failing half-way must still fence its slot.
+  be reallocated while its batch is queued, a launch failing half-way must still fence its slot, and a
+  slot's pinned upload ring must neither overwrite nor free an entry whose copy is still queued.
 * The owned device buffers and the host forms' sequence (coconut-rust_amd/csrc/devbuf.h: upload, launch,
   download, wipe, synchronise) are compiled the same way against a simulated device that logs every
   operation and can fail any one of them (tests/host/test_devbuf.cpp), with LeakSanitizer on.

@@ -535,7 +535,7 @@ def decode(g, enc):
     return a if g.on_curve(a) else None
 
 
-VK_WBITS = 22  # shared-verkey tables (fixed.h; capi.cpp rebuild_tables: the widest of 22 / 20 / 16 bits whose
+VK_WBITS = 22  # shared-verkey tables (fixed.h; capi_ctx.cpp rebuild_tables: the widest of 22 / 20 / 16 bits whose
 # tables fit the HBM budget -- 22 for configs 2 and 3 (8 / 18 G1 bases), 20 for config 5 (34 bases); main()
 # sets it per config)
 
@@ -750,7 +750,7 @@ def _raw_mul(g, a, b):
 
 
 def issuer_wbits(nb, two, budget=16 << 30):
-    """capi.cpp cc_set_issuers: the widest window in {16, 13, 12, 10} whose tables (nb bases, affine
+    """capi_aggregate.cpp cc_set_issuers: the widest window in {16, 13, 12, 10} whose tables (nb bases, affine
     entries of 24 / 48 words) fit the default 16 GiB budget, else 8."""
     for w in (16, 13, 12, 10):
         if nb * ((256 + w - 1) // w) * ((1 << w) - 1) * (48 if two else 24) * 4 <= budget:
