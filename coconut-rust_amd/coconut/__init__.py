@@ -9,7 +9,7 @@ this package on a machine without the built library raises immediately.
 """
 from .errors import CoconutError, CoconutErrorKind  # noqa: F401
 from ._lib import version, source_hash  # noqa: F401
-from .signature import (GroupMode, Params, Verkey, Signature, Context, verify_batch,  # noqa: F401
+from .signature import (GroupMode, Params, Verkey, Signature, Context, verify_batch, verify_batch_locate,  # noqa: F401
                         signature_aggregate_batch, verkey_aggregate_batch, verkey_aggregate_ids, fixed_base_mul, subgroup_check, hash_to_curve, hash_msg, params_new,
                         G1_GENERATOR, G2_GENERATOR)
 from .pok_sig import (PoKOfSignature, PoKOfSignatureProof, pok_verify_batch, pok_init_batch,  # noqa: F401

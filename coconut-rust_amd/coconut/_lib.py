@@ -98,6 +98,10 @@ _SIGS = {
     "cc_rlc_partial_words": (c_int, []),
     "cc_rlc_partial_device": (c_int, [c_p, c_sz, c_sz, ctypes.c_uint64, c_p, c_p, c_p, c_p, c_p, c_p]),
     "cc_rlc_finish_device": (c_int, [c_p, c_sz, c_p, c_p, c_p, c_p]),
+    "cc_rlc_partial_seg_device": (c_int, [c_p, c_sz, c_sz, c_sz, ctypes.c_uint64, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "cc_rlc_finish_each_device": (c_int, [c_p, c_sz, c_p, c_p, c_p, c_p]),
+    "cc_verify_batch_locate_device": (c_int, [c_p, c_sz, c_sz, c_sz, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "cc_verify_batch_locate": (c_int, [c_p, c_sz, c_sz, c_sz, c_p, c_p, c_p, c_p, c_p]),
     "cc_last_timing": (c_int, [c_p, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float),
                                ctypes.POINTER(ctypes.c_float)]),
     "cc_set_timing": (c_int, [c_p, c_int]),

@@ -68,8 +68,12 @@ def rlc_accept(engine, group=None) -> bool:
     return engine.finish(allp, k)
 
 
-def verify_sharded(engine, rlc: bool = True, group=None) -> np.ndarray:
-    """Verdicts (uint8) for this rank's slice; RLC first when requested, per-credential fallback."""
+def verify_sharded(engine, rlc=True, group=None) -> np.ndarray:
+    """Verdicts (uint8) for this rank's slice; RLC first when requested, per-credential fallback.
+    rlc="locate": every rank locates inside its own slice (``engine.locate``: segments with their own RLC
+    checks, per-credential verification of the rejected ones only); no collective at all."""
+    if rlc == "locate":
+        return engine.locate()[0]
     if rlc and rlc_accept(engine, group):
         return np.ones(engine.n, dtype=np.uint8)
     return engine.per_credential()
@@ -179,6 +183,54 @@ class DeviceEngine:
             ev.synchronize()
             return bool(host[0].item())
         return result
+
+    def _ptrs(self):
+        return (ctypes.c_void_p(self.d_s1.data_ptr()), ctypes.c_void_p(self.d_s2.data_ptr()),
+                ctypes.c_void_p(self.d_msgs.data_ptr()))
+
+    def partial_seg(self, seg: int):
+        """cc_rlc_partial_seg_device: one partial per segment of `seg` credentials (a power of two >= 4), a
+        (ceil(n / seg), PARTIAL_WORDS) int32 tensor; partial s is what partial() gives for the slice with
+        base_index + s * seg."""
+        import torch
+        seed = self.seed if self.seed is not None else os.urandom(32)
+        nseg = -(-self.n // seg) if seg > 0 else 0
+        parts = torch.empty((max(nseg, 1), PARTIAL_WORDS), dtype=torch.int32, device=self.dev)
+        self._enter()
+        self._check(self.lib.cc_rlc_partial_seg_device(self.ctx.h, self.n, self.q, seg, self.base_index, seed,
+                                                       *self._ptrs(), ctypes.c_void_p(parts.data_ptr()), self._sh),
+                    "cc_rlc_partial_seg_device")
+        self._leave()
+        return parts[:nseg]
+
+    def finish_each(self, parts, k: int, want_gt: bool = False):
+        """cc_rlc_finish_each_device: one decision per partial, a uint8 array of k (and, with want_gt, the
+        k x 576 GT bytes); decision s is finish(parts[s:s + 1], 1)'s."""
+        import torch
+        parts = parts.contiguous()
+        acc = torch.zeros(k, dtype=torch.uint8, device=self.dev)
+        gt = torch.zeros(k * 576, dtype=torch.uint8, device=self.dev) if want_gt else None
+        self._enter()
+        self._check(self.lib.cc_rlc_finish_each_device(self.ctx.h, k, ctypes.c_void_p(parts.data_ptr()),
+                                                       ctypes.c_void_p(acc.data_ptr()),
+                                                       ctypes.c_void_p(gt.data_ptr()) if want_gt else None,
+                                                       self._sh), "cc_rlc_finish_each_device")
+        self._leave()
+        a = acc.cpu().numpy()
+        return (a, gt.cpu().numpy().tobytes()) if want_gt else a
+
+    def locate(self, seg: int = 0):
+        """cc_verify_batch_locate_device over the slice (deltas from index 0: every slice is checked on its
+        own): (verdicts uint8[n], (segments, rejected segments, credentials rechecked))."""
+        seed = self.seed if self.seed is not None else os.urandom(32)
+        stats = np.zeros(3, dtype=np.uint32)
+        self._enter()
+        self._check(self.lib.cc_verify_batch_locate_device(self.ctx.h, self.n, self.q, seg, seed, *self._ptrs(),
+                                                           ctypes.c_void_p(self.verdicts.data_ptr()),
+                                                           ctypes.c_void_p(stats.ctypes.data), self._sh),
+                    "cc_verify_batch_locate_device")
+        self._leave()
+        return self.verdicts.cpu().numpy(), tuple(int(x) for x in stats)
 
     def per_credential(self) -> np.ndarray:
         self._enter()

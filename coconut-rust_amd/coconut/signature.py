@@ -314,6 +314,25 @@ def verify_batch(ctx: Context, n: int, q: int, sigma1: bytes, sigma2: bytes, msg
     return verdicts[:n]
 
 
+def verify_batch_locate(ctx: Context, n: int, q: int, sigma1: bytes, sigma2: bytes, msgs: bytes, seg: int = 0):
+    """Batch Signature::verify through the RLC locate mode (cc_verify_batch_locate; shared verkey): the
+    batch is checked in segments of `seg` credentials (a power of two >= 4; 0: the library's default) and
+    only the rejected segments are verified per credential.  Returns (verdicts uint8[n], stats) with
+    stats = (segments, rejected segments, credentials rechecked); the verdicts equal verify_batch's."""
+    sb = ctx.mode.sig_bytes
+    need(sigma1, n * sb, "sigma_1")
+    need(sigma2, n * sb, "sigma_2")
+    need(msgs, n * q * 48, "messages")
+    verdicts = np.zeros(max(n, 1), dtype=np.uint8)
+    stats = np.zeros(3, dtype=np.uint32)
+    p1, k1 = buf(sigma1)
+    p2, k2 = buf(sigma2)
+    pm, k3 = buf(msgs)
+    check(lib.cc_verify_batch_locate(ctx.h, n, q, seg, p1, p2, pm, ctypes.c_void_p(verdicts.ctypes.data),
+                                     ctypes.c_void_p(stats.ctypes.data)), "cc_verify_batch_locate")
+    return verdicts[:n], tuple(int(x) for x in stats)
+
+
 def signature_aggregate_batch(ctx: Context, n: int, length: int, t: int, ids, sigma1: bytes, sigma2: bytes):
     sb = ctx.mode.sig_bytes
     ids = np.ascontiguousarray(np.asarray(ids, dtype=np.uint64).reshape(n, length))

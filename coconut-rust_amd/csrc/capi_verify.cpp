@@ -1,7 +1,6 @@
 // C ABI, Signature::verify: the verify launches, the device and host forms, the RLC partial and finish, and
-// the sharded verify of a device set (ctx.h).
-#include <thread>
-
+// the sharded verify of a device set (ctx.h).  The segmented partial, the per-partial finish and the locate
+// drivers: capi_locate.cpp.
 #include "ctx.h"
 
 // Small batches run latency-bound: their Miller loops one wave per pair (n <= kWideMax: miller_wide.hip
@@ -232,20 +231,6 @@ cc_status cc::host::write_neutral_partial(uint32_t* d_partial, hipStream_t st) {
         return v;
     }();
     HIPCK(hipMemcpyAsync(d_partial, kNeutral.data(), RLC_PART_WORDS * 4, hipMemcpyHostToDevice, st));
-    return CC_OK;
-}
-
-// run f(k, lo, hi) for every peer k on its own host thread over the contiguous shard [lo, hi)
-template <class F>
-static cc_status for_shards(cc_ctx* c, size_t n, F f) {
-    const size_t k = c->peers.size();
-    std::vector<cc_status> st(k, CC_OK);
-    std::vector<std::thread> th;
-    for (size_t d = 0; d < k; d++)
-        th.emplace_back([&, d] { st[d] = f(d, n * d / k, n * (d + 1) / k); });
-    for (auto& t : th) t.join();
-    for (cc_status s : st)
-        if (s) return s;
     return CC_OK;
 }
 

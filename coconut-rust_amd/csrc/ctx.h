@@ -12,11 +12,13 @@
 #include <rccl/rccl.h>
 
 #include <algorithm>
+#include <thread>
 #include <vector>
 
 #include "../../include/coconut_hip.h"
 #include "devbuf.h"
 #include "launch.h"
+#include "locate_plan.h"
 #include "rlc_part.h"
 #include "slots.h"
 
@@ -139,6 +141,10 @@ struct cc_ctx {
     DevBuf fin_f, fin_scratch, fin_prep, fin_flags2, fin_part;
     hipEvent_t ev_fin = nullptr;  // end of the last finish: finishes of one context run in call order
     bool fin_recorded = false;
+    // the segmented partial, the per-partial finish and the locate drivers (capi_locate.cpp): one fall-back
+    // word per segment, the segmented fold's workspace, the per-partial flags of a finish; the drivers'
+    // segment partials and accept bytes, and the compacted rows and verdicts of the rejected segments
+    DevBuf seg_any, seg_work, fin_each_flags, loc_parts, loc_accept, loc_s1, loc_s2, loc_msgs, loc_verdicts;
     // RLC g~-side fold (fold.hip): fold points, delta digits, sort/partials/bucket workspace; the fixed
     // points P_w = (256^w) g~ of the window pairs (SoA, built with the verkey tables) and their
     // identity flags
@@ -287,6 +293,19 @@ cc_status launch_rlc_partial(cc_ctx* c, const RlcWork& w, size_t n, size_t q, ui
                              const uint8_t* d_s1, const uint8_t* d_s2, const uint8_t* d_msgs, uint32_t* d_partial,
                              hipStream_t st, Staging* stage, const PokRlcArgs* pok = nullptr);
 cc_status write_neutral_partial(uint32_t* d_partial, hipStream_t st);
+// run f(k, lo, hi) for every peer k of a device set on its own host thread over the contiguous shard [lo, hi)
+template <class F>
+static cc_status for_shards(cc_ctx* c, size_t n, F f) {
+    const size_t k = c->peers.size();
+    std::vector<cc_status> st(k, CC_OK);
+    std::vector<std::thread> th;
+    for (size_t d = 0; d < k; d++)
+        th.emplace_back([&, d] { st[d] = f(d, n * d / k, n * (d + 1) / k); });
+    for (auto& t : th) t.join();
+    for (cc_status s : st)
+        if (s) return s;
+    return CC_OK;
+}
 // The RLC host forms (cc_verify_batch, cc_pok_verify_batch_rlc) behind the uploads f has queued, as two
 // sequences: partial(seed) queues the form's partial into c->rlc_part, then the finish and `accept` down,
 // which ends f; only on reject (a bad element somewhere) a second one, each(g), takes the per-element launch

@@ -27,6 +27,8 @@
 //                                                 per bucket or window, 2 waves/SIMD where the one-lane
 //                                                 G2 forms need 448-512 registers (1 wave/SIMD)
 //   k_fold_fixed<F>                             : the fixed points P_w (once per verkey, cck_fold_fixed)
+//   k_fold_*_seg                                : the same fold for every segment of a batch at once
+//                                                 (cc_rlc_partial_seg_device; below, after the above)
 // X_i = -sigma_2,i (AoS affine in the lazy field's form, fixed.h fp_to_lazy_form; written by the RLC
 // prep); S_w lands in the shard's partial (rlc_part.h: affine words + identity flag per window), and
 // the finish pairs every shard's S_w with P_w (rlc.hip k_rlc_gather, then miller_wide.hip k_miller_wide): SigG2 S in
@@ -333,6 +335,273 @@ __global__ __launch_bounds__(64) void k_fold_fixed(int q, const uint32_t* __rest
     else st_as_q(S, w, a);                                     // SigG1: g~ in G2
 }
 
+// ---------------------------------------------------------------- the segmented fold
+// cc_rlc_partial_seg_device: the same sort, bucket sums and window sums for every segment of `seg`
+// credentials (segment s: credentials [s seg, min(n, (s + 1) seg))), each with its own 2,048 buckets and
+// a fixed region of the list / chunk / bucket buffers (mcs = fold_maxchunks(seg) chunks a segment), so
+// segment s's window sums are those of the unsegmented fold over its slice and land in partial s.  The
+// digits and fold points keep the batch's layout (dig[w * n + i], pts[i]); list entries hold the batch
+// index i.  Segments run along the grid's x dimension (up to CC_MAX_PARTS of them).
+
+__global__ __launch_bounds__(256) void k_fold_count_seg(size_t n, size_t seg, const int8_t* __restrict__ dig,
+                                                        uint32_t* __restrict__ cnt) {
+    __shared__ uint32_t h[FD];
+    const size_t s = blockIdx.x;
+    const int w = blockIdx.y;
+    const size_t lo = s * seg, hi = lo + seg < n ? lo + seg : n;
+    for (int t = threadIdx.x; t < FD; t += blockDim.x) h[t] = 0;
+    __syncthreads();
+    for (size_t i = lo + blockIdx.z * (size_t)blockDim.x + threadIdx.x; i < hi; i += (size_t)gridDim.z * blockDim.x) {
+        const int d = dig[(size_t)w * n + i];
+        if (d) atomicAdd(&h[(d < 0 ? -d : d) - 1], 1u);
+    }
+    __syncthreads();
+    for (int t = threadIdx.x; t < FD; t += blockDim.x)
+        if (h[t]) atomicAdd(&cnt[s * FB + w * FD + t], h[t]);
+}
+
+// k_fold_scan, one block per segment: offsets inside the segment's own list region
+__global__ __launch_bounds__(256) void k_fold_scan_seg(const uint32_t* __restrict__ cnt, uint32_t* __restrict__ off,
+                                                       uint32_t* __restrict__ cur) {
+    constexpr int PT = FB / 256;
+    __shared__ uint32_t sm[256];
+    const size_t s = blockIdx.x;
+    cnt += s * FB, off += s * (FB + 1), cur += s * FB;
+    const int t = threadIdx.x;
+    uint32_t loc[PT], pc[PT], sum = 0;
+#pragma unroll
+    for (int k = 0; k < PT; k++) {
+        pc[k] = (cnt[t * PT + k] + FS - 1) / FS * FS;
+        loc[k] = sum;
+        sum += pc[k];
+    }
+    sm[t] = sum;
+    __syncthreads();
+    for (int o = 1; o < 256; o <<= 1) {
+        const uint32_t v = t >= o ? sm[t - o] : 0u;
+        __syncthreads();
+        sm[t] += v;
+        __syncthreads();
+    }
+    const uint32_t base = t ? sm[t - 1] : 0u;
+#pragma unroll
+    for (int k = 0; k < PT; k++) {
+        const int b = t * PT + k;
+        const uint32_t o = base + loc[k];
+        off[b] = o;
+        cur[b] = o;
+    }
+    if (t == 255) off[FB] = sm[255];
+}
+
+__global__ __launch_bounds__(256) void k_fold_scatter_seg(size_t n, size_t seg, size_t mcs,
+                                                          const int8_t* __restrict__ dig, uint32_t* __restrict__ cur,
+                                                          uint32_t* __restrict__ list) {
+    const size_t s = blockIdx.x;
+    const int w = blockIdx.y;
+    const size_t lo = s * seg, hi = lo + seg < n ? lo + seg : n;
+    for (size_t i = lo + blockIdx.z * (size_t)blockDim.x + threadIdx.x; i < hi; i += (size_t)gridDim.z * blockDim.x) {
+        const int d = dig[(size_t)w * n + i];
+        if (!d) continue;
+        const uint32_t pos = atomicAdd(&cur[s * FB + w * FD + (d < 0 ? -d : d) - 1], 1u);
+        list[s * mcs * FS + pos] = (uint32_t)i | (d < 0 ? 0x80000000u : 0u);
+    }
+}
+
+// k_fold_sum_g1 over the chunks of every segment: chunk c is chunk c % mcs of segment c / mcs
+__global__ __launch_bounds__(256) void k_fold_sum_g1_seg(size_t nseg, size_t mcs, const uint32_t* __restrict__ off,
+                                                         const uint32_t* __restrict__ list,
+                                                         const uint32_t* __restrict__ pts,
+                                                         uint32_t* __restrict__ part) {
+    constexpr int AW = sizeof(Aff<Fp>) / 4, JW = sizeof(Jac<Fp>) / 4;
+    const size_t c = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    const size_t s = c / mcs;
+    if (s >= nseg || (c - s * mcs) * FS >= off[s * (FB + 1) + FB]) return;
+    lz::JG acc = lz::jg_inf();
+#pragma unroll 1
+    for (int e = 0; e < FS; e++) {
+        const uint32_t v = list[c * FS + e];
+        if (v == PAD) continue;
+        Aff<Fp> a;
+        ld_aff_aos<Fp>(a, pts + (size_t)(v & 0x7fffffffu) * AW);
+        const auto y = lz::from_fp(a.y);
+        acc = lz::jg_add_aff(acc, lz::AG{lz::from_fp(a.x), lz::sel((v >> 31) != 0, lz::neg(y), y)});
+    }
+    st_jac_aos<Fp>(part + c * JW, lz::jg_to(acc));
+}
+
+// lane_group_sum / pair_group_sum (curve.h, curve_pl.h) over groups of gl consecutive lanes, gl a power of
+// two <= 64 known only at launch; every lane of the wave takes part
+template <class F>
+DEV void lane_group_sum_rt(Jac<F>& acc, int gl, int m_last) {
+    constexpr int JW = sizeof(Jac<F>) / 4;
+#pragma unroll 1
+    for (int m = gl >> 1; m >= m_last; m >>= 1) {
+        Jac<F> o;
+        const uint32_t* a = reinterpret_cast<const uint32_t*>(&acc);
+        uint32_t* w = reinterpret_cast<uint32_t*>(&o);
+        for (int c = 0; c < JW; c++) w[c] = (uint32_t)__shfl_xor((int)a[c], m);
+        if (threadIdx.x & m) {  // same operand order on both partners
+            Jac<F> t = acc;
+            acc = o;
+            o = t;
+        }
+        jac_add(acc, acc, o);
+    }
+}
+
+// k_fold_reduce<Fp> for (segment, bucket) s * FB + b, gl lanes a bucket: a short segment's bucket holds a
+// chunk or two (16 seg entries over 2,048 buckets), so a whole wave a bucket would mostly add identities;
+// the launcher picks gl from seg (fold_seg_group), 64 / gl buckets a wave
+__global__ __launch_bounds__(64) void k_fold_reduce_g1_seg(size_t mcs, int gl, const uint32_t* __restrict__ off,
+                                                           const uint32_t* __restrict__ part,
+                                                           uint32_t* __restrict__ bkt) {
+    constexpr int JW = sizeof(Jac<Fp>) / 4;
+    const size_t gb = (blockIdx.x * (size_t)64 + threadIdx.x) / gl;  // the grid holds whole groups only
+    const int lt = threadIdx.x % gl;
+    const size_t s = gb / FB;
+    const int b = (int)(gb % FB);
+    const uint32_t* o = off + s * (FB + 1);
+    const uint32_t c0 = o[b] / FS, c1 = o[b + 1] / FS;
+    Jac<Fp> acc;
+    jac_set_inf(acc);
+#pragma unroll 1
+    for (uint32_t c = c0 + lt; c < c1; c += gl) {
+        Jac<Fp> p;
+        ld_jac_aos<Fp>(p, part + (s * mcs + c) * JW);
+        jac_add(acc, acc, p);
+    }
+    lane_group_sum_rt<Fp>(acc, gl, 1);
+    if (lt == 0) st_jac_aos<Fp>(bkt + gb * JW, acc);
+}
+
+// k_fold_window, one wave per (segment, window): block s * FW + w, into partial s
+__global__ __launch_bounds__(64) void k_fold_window_seg(const uint32_t* __restrict__ bkt, uint32_t* __restrict__ parts) {
+    constexpr int JW = sizeof(Jac<Fp>) / 4, CK = FD / 64;
+    const size_t s = blockIdx.x / FW;
+    const int w = (int)(blockIdx.x % FW), t = threadIdx.x;
+    bkt += s * FB * JW;
+    lz::JG run = lz::jg_inf(), u = lz::jg_inf(), v = lz::jg_inf();
+#pragma unroll 1
+    for (int k = CK - 1; k >= 0; k--) {
+        Jac<Fp> b;
+        ld_jac_aos<Fp>(b, bkt + (size_t)(w * FD + CK * t + k) * JW);
+        run = lz::jg_add(run, lz::jg_from(b));
+        u = lz::jg_add(u, run);
+    }
+#pragma unroll 1
+    for (int sh = 5; sh >= 0; sh--) {  // [t] run (t < 64), then [CK] of it
+        v = lz::jg_dbl(v);
+        if ((t >> sh) & 1) v = lz::jg_add(v, run);
+    }
+#pragma unroll 1
+    for (int c = 1; c < CK; c <<= 1) v = lz::jg_dbl(v);
+    Jac<Fp> acc = lz::jg_to(lz::jg_add(u, v));
+    lane_group_sum<Fp, 64>(acc);
+    if (threadIdx.x != 0) return;
+    Aff<Fp> a;
+    const bool fin = jac_to_aff(a, acc);
+    uint32_t* o = parts + s * RLC_PART_WORDS + RLC_WIN_OFF + RLC_WIN_WORDS * w;
+#pragma unroll
+    for (int k = 0; k < NL; k++) {
+        o[k] = fin ? a.x.v[k] : 0u;
+        o[NL + k] = fin ? a.y.v[k] : 0u;
+        o[2 * NL + k] = 0u;
+        o[3 * NL + k] = 0u;
+    }
+    o[4 * NL] = fin ? 0u : 1u;  // e(O, .) = 1: the finish skips the pair
+}
+
+// the pair-lane G2 forms (SigG2), as k_fold_sum_g2pl / k_fold_reduce_g2pl / k_fold_window_g2pl
+__global__ __launch_bounds__(256, 2) void k_fold_sum_g2pl_seg(size_t nseg, size_t mcs, const uint32_t* __restrict__ off,
+                                                              const uint32_t* __restrict__ list,
+                                                              const uint32_t* __restrict__ pts,
+                                                              uint32_t* __restrict__ part) {
+    constexpr int AW = sizeof(Aff<Fp2>) / 4, JW = sizeof(Jac<Fp2>) / 4, HW = sizeof(Jac<pl::Fp2>) / 4;
+    const size_t c = (blockIdx.x * (size_t)blockDim.x + threadIdx.x) >> 1;  // pair-uniform
+    const int h = (int)pl::half_id();
+    const size_t s = c / mcs;
+    if (s >= nseg || (c - s * mcs) * FS >= off[s * (FB + 1) + FB]) return;
+    lz::JL acc = lz::jl_inf();
+#pragma unroll 1
+    for (int e = 0; e < FS; e++) {
+        const uint32_t v = list[c * FS + e];  // pair-uniform
+        if (v == PAD) continue;
+        const uint32_t* p = pts + (size_t)(v & 0x7fffffffu) * AW;
+        Fp x, y;
+#pragma unroll
+        for (int k = 0; k < NL; k++) {
+            x.v[k] = p[NL * h + k];
+            y.v[k] = p[2 * NL + NL * h + k];
+        }
+        const lz::F2<lz::AN, lz::BC> ly{lz::from_fp(y)};
+        const lz::F2<lz::AN, lz::BC> qy{lz::sel((v >> 31) != 0, lz::neg(ly).c, ly.c)};
+        acc = lz::jl_add_aff_c(acc, lz::F2<lz::AN, lz::BC>{lz::from_fp(x)}, qy);
+    }
+    st_jac_aos<pl::Fp2>(part + c * JW + h * HW, pl::jl_to_pl(acc));
+}
+
+// gl lanes (gl / 2 lane pairs) a bucket, as k_fold_reduce_g1_seg; the butterfly stops at distance 2, so
+// halves stay with halves
+__global__ __launch_bounds__(64, 2) void k_fold_reduce_g2pl_seg(size_t mcs, int gl, const uint32_t* __restrict__ off,
+                                                               const uint32_t* __restrict__ part,
+                                                               uint32_t* __restrict__ bkt) {
+    constexpr int JW = sizeof(Jac<Fp2>) / 4, HW = sizeof(Jac<pl::Fp2>) / 4;
+    const size_t gb = (blockIdx.x * (size_t)64 + threadIdx.x) / gl;  // the grid holds whole groups only
+    const int lt = threadIdx.x % gl;  // pair lt >> 1 of the group
+    const size_t s = gb / FB;
+    const int b = (int)(gb % FB);
+    const int h = (int)pl::half_id();
+    const uint32_t* o = off + s * (FB + 1);
+    const uint32_t c0 = o[b] / FS, c1 = o[b + 1] / FS;
+    Jac<pl::Fp2> acc;
+    jac_set_inf(acc);
+#pragma unroll 1
+    for (uint32_t c = c0 + (lt >> 1); c < c1; c += gl >> 1) {  // pair-uniform
+        Jac<pl::Fp2> p;
+        ld_jac_aos<pl::Fp2>(p, part + (s * mcs + c) * JW + h * HW);
+        jac_add(acc, acc, p);
+    }
+    lane_group_sum_rt<pl::Fp2>(acc, gl, 2);
+    if (lt < 2) st_jac_aos<pl::Fp2>(bkt + gb * JW + h * HW, acc);
+}
+
+__global__ __launch_bounds__(64, 2) void k_fold_window_g2pl_seg(const uint32_t* __restrict__ bkt,
+                                                               uint32_t* __restrict__ parts) {
+    constexpr int JW = sizeof(Jac<Fp2>) / 4, HW = sizeof(Jac<pl::Fp2>) / 4, CK = FD / 32;
+    const size_t s = blockIdx.x / FW;
+    const int w = (int)(blockIdx.x % FW), t = threadIdx.x >> 1;  // pair-uniform
+    const int h = (int)pl::half_id();
+    bkt += s * FB * JW;
+    lz::JL run = lz::jl_inf(), u = lz::jl_inf(), v = lz::jl_inf();
+#pragma unroll 1
+    for (int k = CK - 1; k >= 0; k--) {  // running sums: run = sum B, u = sum (k + 1) B
+        Jac<pl::Fp2> b;
+        ld_jac_aos<pl::Fp2>(b, bkt + (size_t)(w * FD + CK * t + k) * JW + h * HW);
+        run = lz::jl_add(run, pl::jl_from_pl(b));
+        u = lz::jl_add(u, run);
+    }
+#pragma unroll 1
+    for (int sh = 4; sh >= 0; sh--) {  // [t] run (t < 32), then [CK] of it
+        v = lz::jl_dbl(v);
+        if ((t >> sh) & 1) v = lz::jl_add(v, run);
+    }
+#pragma unroll 1
+    for (int c = 1; c < CK; c <<= 1) v = lz::jl_dbl(v);
+    Jac<pl::Fp2> acc = pl::jl_to_pl(lz::jl_add(u, v));
+    pl::pair_group_sum<64>(acc);
+    if (threadIdx.x >= 2) return;
+    Aff<pl::Fp2> a;
+    const bool fin = jac_to_aff(a, acc);  // pair-uniform
+    uint32_t* o = parts + s * RLC_PART_WORDS + RLC_WIN_OFF + RLC_WIN_WORDS * w;
+#pragma unroll
+    for (int k = 0; k < NL; k++) {
+        o[NL * h + k] = fin ? a.x.c.v[k] : 0u;
+        o[2 * NL + NL * h + k] = fin ? a.y.c.v[k] : 0u;
+    }
+    if (!h) o[4 * NL] = fin ? 0u : 1u;  // e(O, .) = 1: the finish skips the pair
+}
+
 static inline unsigned nblocks(size_t n, unsigned bs) { return (unsigned)((n + bs - 1) / bs); }
 
 // work-buffer layout (32-bit words): cnt FB | off FB+1 | cur FB (+3) | list maxchunks*FS |
@@ -408,6 +677,77 @@ int cck_fold_window(int mode, size_t n, uint32_t* d_work, uint32_t* d_partial, h
         hipLaunchKernelGGL(k_fold_window_g2pl, dim3(FW), dim3(64), 0, st, bkt, d_partial);
     else
         hipLaunchKernelGGL(k_fold_window, dim3(FW), dim3(64), 0, st, bkt, d_partial);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// the segmented fold's work buffer: cnt S FB | off S (FB + 1) | cur S FB (+3) | list S mcs FS |
+// part S mcs JW (16-byte aligned) | bkt S FB JW, with S = ceil(n / seg) and mcs = fold_maxchunks(seg)
+static FoldWork fold_work_seg(int mode, size_t nseg, size_t seg, uint32_t* d_work) {
+    const size_t mcs = fold_maxchunks(seg);
+    FoldWork w;
+    w.cnt = d_work;
+    w.off = w.cnt + nseg * FB;
+    w.cur = w.off + nseg * (FB + 1);
+    w.list = w.cur + nseg * FB + 3;
+    w.part = reinterpret_cast<uint32_t*>(((uintptr_t)(w.list + nseg * mcs * FS) + 15) & ~(uintptr_t)15);
+    w.bkt = w.part + nseg * mcs * (mode == 0 ? sizeof(Jac<Fp2>) / 4 : sizeof(Jac<Fp>) / 4);
+    return w;
+}
+
+// lanes a bucket in the segmented reduce: a bucket expects seg / 2,048 chunks (+ a partly filled one); the
+// next power of two of that many lanes (SigG2: lane pairs), up to the whole wave of the unsegmented form
+static int fold_seg_group(int mode, size_t seg) {
+    int g = 1;
+    while (g < 64 && (size_t)g * 2048 < seg) g <<= 1;
+    if (mode == 0) g = g >= 32 ? 64 : 2 * g;
+    return g;
+}
+
+size_t cck_fold_seg_words(int mode, size_t n, size_t seg) {
+    if (!seg) return 0;
+    const size_t jw = mode == 0 ? sizeof(Jac<Fp2>) / 4 : sizeof(Jac<Fp>) / 4;
+    const size_t S = (n + seg - 1) / seg, mcs = fold_maxchunks(seg);
+    return S * (3 * (size_t)FB + 1) + 3 + S * mcs * FS + S * mcs * jw + 4 + S * (size_t)FB * jw;
+}
+
+// cck_fold for every segment of seg credentials (d_work: cck_fold_seg_words words); cck_fold_window_seg
+// then writes segment s's window sums into partial s of d_partials
+int cck_fold_seg(int mode, size_t n, size_t seg, const int8_t* d_dig, const uint32_t* d_pts, uint32_t* d_work,
+                 hipStream_t st) {
+    if (!n || !seg) return -1;
+    const size_t S = (n + seg - 1) / seg, mcs = fold_maxchunks(seg);
+    const FoldWork fw = fold_work_seg(mode, S, seg, d_work);
+    if (hipMemsetAsync(fw.cnt, 0, S * FB * 4, st) != hipSuccess ||
+        hipMemsetAsync(fw.list, 0xff, S * mcs * FS * 4, st) != hipSuccess)
+        return -1;
+    const size_t span = seg < n ? seg : n;
+    const size_t gl = (size_t)fold_seg_group(mode, seg);  // S FB gl is a multiple of 64: whole waves
+    const dim3 gw((unsigned)S, FW, nblocks(span, 256) < 64 ? nblocks(span, 256) : 64);
+    hipLaunchKernelGGL(k_fold_count_seg, gw, dim3(256), 0, st, n, seg, d_dig, fw.cnt);
+    hipLaunchKernelGGL(k_fold_scan_seg, dim3((unsigned)S), dim3(256), 0, st, fw.cnt, fw.off, fw.cur);
+    hipLaunchKernelGGL(k_fold_scatter_seg, gw, dim3(256), 0, st, n, seg, mcs, d_dig, fw.cur, fw.list);
+    if (mode == 0) {
+        hipLaunchKernelGGL(k_fold_sum_g2pl_seg, dim3(nblocks(2 * S * mcs, 256)), dim3(256), 0, st, S, mcs, fw.off,
+                           fw.list, d_pts, fw.part);
+        hipLaunchKernelGGL(k_fold_reduce_g2pl_seg, dim3((unsigned)(S * FB * gl / 64)), dim3(64), 0, st, mcs, (int)gl, fw.off,
+                           fw.part, fw.bkt);
+    } else {
+        hipLaunchKernelGGL(k_fold_sum_g1_seg, dim3(nblocks(S * mcs, 256)), dim3(256), 0, st, S, mcs, fw.off, fw.list,
+                           d_pts, fw.part);
+        hipLaunchKernelGGL(k_fold_reduce_g1_seg, dim3((unsigned)(S * FB * gl / 64)), dim3(64), 0, st, mcs, (int)gl, fw.off,
+                           fw.part, fw.bkt);
+    }
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int cck_fold_window_seg(int mode, size_t n, size_t seg, uint32_t* d_work, uint32_t* d_partials, hipStream_t st) {
+    if (!n || !seg) return -1;
+    const size_t S = (n + seg - 1) / seg;
+    uint32_t* bkt = fold_work_seg(mode, S, seg, d_work).bkt;
+    if (mode == 0)
+        hipLaunchKernelGGL(k_fold_window_g2pl_seg, dim3((unsigned)(S * FW)), dim3(64), 0, st, bkt, d_partials);
+    else
+        hipLaunchKernelGGL(k_fold_window_seg, dim3((unsigned)(S * FW)), dim3(64), 0, st, bkt, d_partials);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

@@ -292,11 +292,18 @@ __global__ __launch_bounds__(MB, 2) void k_miller(size_t n, size_t ps, const uin
 // in LDS (4 x 39 words a lane: the whole 160 KiB of a CU at 1 wave/SIMD, 256 lanes), the loop body is
 // the two-pair loop's with one pair at a time; the product of the four Miller values goes to element
 // foff + j.
+// CC_MILLER_SEG (its own object again, Makefile miller4s_*: the segmented RLC partial): qcheck holds one
+// word per segment of 4 << qshift credentials, and the four credentials of loop j share word j >> qshift.
+#ifdef CC_MILLER_SEG
+#define CC_MILLER_QSHIFT_PARAM , int qshift
+#else
+#define CC_MILLER_QSHIFT_PARAM
+#endif
 template <int SIG>
 __global__ __launch_bounds__(MB, 1) void k_miller4(size_t n, size_t ps, const uint32_t* __restrict__ prep,
                                                 const uint32_t* __restrict__ flags, uint32_t* __restrict__ fout,
                                                 size_t fstride, size_t foff, uint32_t* __restrict__ qcheck,
-                                                int pform) {
+                                                int pform CC_MILLER_QSHIFT_PARAM) {
     constexpr int NP = 4;
     __shared__ int32_t lds[NP * TP][MB];
     const size_t j = (blockIdx.x * (size_t)blockDim.x + threadIdx.x) >> 1;
@@ -340,6 +347,9 @@ __global__ __launch_bounds__(MB, 1) void k_miller4(size_t n, size_t ps, const ui
         }
     }
     if (SIG == 2 && qcheck) {
+#ifdef CC_MILLER_SEG
+        qcheck += j >> qshift;  // the segment's word, outside the loop
+#endif
 #pragma unroll 1
         for (int k = 0; k < NP; k++) {
             if ((skipm >> k) & 1u) continue;  // pair-uniform
@@ -359,7 +369,23 @@ __global__ __launch_bounds__(MB, 1) void k_miller4(size_t n, size_t ps, const ui
 }  // namespace lz
 }  // namespace cc
 
-#ifdef CC_MILLER_QUAD
+#if defined(CC_MILLER_QUAD) && defined(CC_MILLER_SEG)
+// k_miller4 with one d_qcheck word per segment of 4 << qshift credentials (ceil(n / (4 << qshift)) words):
+// otherwise cck_miller4_lz_g2.  SigG2 only: SigG1 has no T-based test (d_qcheck is null there), so the
+// segmented partial launches cck_miller4_lz_g1 as it is.
+extern "C" int cck_miller4_seg_lz_g2(size_t n, size_t pstride, const uint32_t* d_prep, const uint32_t* d_flags,
+                                     uint32_t* d_f, size_t fstride, size_t foff, uint32_t* d_qcheck, int qshift,
+                                     hipStream_t st) {
+    static_assert(CC_MILLER_SIG == 2, "the segmented launch is SigG2's");
+    if (!n) return 0;
+    const size_t m = (n + 3) / 4;
+    if (fstride < foff + m || pstride < (n + 1) / 2 || qshift < 0 || qshift > 62) return -1;
+    constexpr int MB = cc::lz::MB;
+    hipLaunchKernelGGL((cc::lz::k_miller4<2>), dim3((unsigned)((2 * m + MB - 1) / MB)), dim3(MB), 0, st, n, pstride,
+                       d_prep, d_flags, d_f, fstride, foff, d_qcheck, (int)cc::lz::kAffRp, qshift);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+#elif defined(CC_MILLER_QUAD)
 #if CC_MILLER_SIG == 2
 #define CC_MILLER4_LAUNCH cck_miller4_lz_g2
 #else

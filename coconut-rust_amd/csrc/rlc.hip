@@ -259,6 +259,40 @@ __global__ void k_rlc_partial_out(const uint32_t* __restrict__ f1, const uint32_
     if (t == RLC_FLAG) partial[t] = *any ? 1u : 0u;
 }
 
+// ---- the segmented partial (cc_rlc_partial_seg_device): one partial per segment of 1 << segsh credentials
+// any[i >> segsh] for every credential with an identity or non-subgroup sigma (flag bits 0, 1, 5 of
+// k_rlc_check_*, which keep raising their single word)
+__global__ __launch_bounds__(256) void k_rlc_seg_flags(size_t n, int segsh, const uint32_t* __restrict__ flags,
+                                                       uint32_t* __restrict__ any) {
+    const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (i < n && (flags[i] & 35u)) atomicOr(any + (i >> segsh), 1u);
+}
+
+// k_rlc_partial_out for the tree level that has nseg elements (SoA stride nseg): block s writes partial
+// s's product and flag words; force: a verkey or g~ outside the subgroup flags every segment
+__global__ void k_rlc_partial_out_seg(size_t nseg, const uint32_t* __restrict__ f, const uint32_t* __restrict__ any,
+                                      uint32_t force, uint32_t* __restrict__ partials) {
+    const size_t s = blockIdx.x;
+    const int t = threadIdx.x;
+    uint32_t* P = partials + s * RLC_PART_WORDS;
+    if (t < RLC_F12_WORDS) P[t] = f[(size_t)t * nseg + s];
+    if (t == RLC_FLAG) P[t] = (force || any[s]) ? 1u : 0u;
+}
+
+// ---- the per-partial finish (cc_rlc_finish_each_device): out[r] = w[r] * (partial r's Miller product), w
+// the product of partial r's 16 window values; SoA stride k, one product per lane pair as k_f12_reduce
+__global__ __launch_bounds__(256) void k_f12_mul_part(size_t k, const uint32_t* __restrict__ w,
+                                                      const uint32_t* __restrict__ parts, uint32_t* __restrict__ out) {
+    const size_t r = (blockIdx.x * (size_t)blockDim.x + threadIdx.x) >> 1;
+    if (r >= k) return;  // pair-uniform
+    const Soa W{const_cast<uint32_t*>(w), k}, P{const_cast<uint32_t*>(parts + r * RLC_PART_WORDS), 1}, O{out, k};
+    pl::Fp12 a, b;
+    pl::ld_f12(a, W, r);
+    pl::ld_f12(b, P, 0);
+    pl::f12_mul(a, a, b);
+    pl::st_f12(O, r, a);
+}
+
 // The finish's inputs from k gathered partials (stride RLC_PART_WORDS), one block per partial r:
 //   fw element r (SoA stride fs)         : partial r's Miller product
 //   window pair e = 16 r + w (prep SoA of stride 16 k, soa.h slots; k_miller_wide's operands): S_w of
@@ -266,7 +300,9 @@ __global__ void k_rlc_partial_out(const uint32_t* __restrict__ f1, const uint32_
 //                                          identity flags); flags2[e] bit 0 skips it (S_w = O or P_w = O)
 //   flag (block 0)                       : OR of the partials' fall-back flags
 // SigG2: S_w in G2 is the Q side, P_w (G1, evaluation form (x, y, 1)) the P side; SigG1 the reverse.
-template <int MODE>
+// EACH (cc_rlc_finish_each_device): every partial is finished on its own, so its product stays where it
+// is (k_f12_mul_part reads it from the partial) and flag[r] is partial r's own fall-back flag.
+template <int MODE, bool EACH = false>
 __global__ __launch_bounds__(256) void k_rlc_gather(size_t k, const uint32_t* __restrict__ parts,
                                                     const uint32_t* __restrict__ pw, const uint8_t* __restrict__ finf,
                                                     uint32_t* __restrict__ fw, size_t fs, uint32_t* __restrict__ prep,
@@ -274,7 +310,11 @@ __global__ __launch_bounds__(256) void k_rlc_gather(size_t k, const uint32_t* __
     const size_t r = blockIdx.x;
     const int t = threadIdx.x;
     const uint32_t* P = parts + r * RLC_PART_WORDS;
-    if (t < RLC_F12_WORDS) fw[(size_t)t * fs + r] = P[t];
+    if constexpr (EACH) {
+        if (t == 255) flag[r] = P[RLC_FLAG] ? 1u : 0u;
+    } else {
+        if (t < RLC_F12_WORDS) fw[(size_t)t * fs + r] = P[t];
+    }
     if (t >= RLC_F12_WORDS && t < RLC_F12_WORDS + RLC_WINDOWS) {
         const int w = t - RLC_F12_WORDS;
         const size_t e = RLC_WINDOWS * r + w;
@@ -304,7 +344,7 @@ __global__ __launch_bounds__(256) void k_rlc_gather(size_t k, const uint32_t* __
         }
         flags2[e] = (win[4 * NL] || finf[w]) ? 1u : 0u;
     }
-    if (r == 0 && t == 255) {
+    if (!EACH && r == 0 && t == 255) {
         uint32_t fl = 0;
         for (size_t p = 0; p < k; p++) fl |= parts[p * RLC_PART_WORDS + RLC_FLAG];
         *flag = fl ? 1u : 0u;
@@ -383,6 +423,72 @@ int cck_rlc_gather(int mode, size_t k, const uint32_t* d_parts, const uint32_t* 
     else
         hipLaunchKernelGGL(k_rlc_gather<1>, dim3((unsigned)k), dim3(256), 0, st, k, d_parts, d_pw, d_finf, d_fw, fs,
                            d_prep, d_flags2, d_flag);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// one level of the product tree: n_in values of src to (n_in + 1) / 2 of dst (cck_rlc_reduce's choice of form)
+static void reduce_level(size_t n, const uint32_t* src, uint32_t* dst, hipStream_t st) {
+    const size_t n_out = (n + 1) / 2;
+    if (n_out <= kWideLevel) (void)cck_f12_reduce_wide(n, src, dst, st);
+    else hipLaunchKernelGGL(k_f12_reduce, dim3(nblocks(2 * n_out, 256)), dim3(256), 0, st, n, src, dst);
+}
+
+// the segmented partial's per-credential flags to one word per segment of 1 << segsh credentials
+int cck_rlc_seg_flags(size_t n, int segsh, const uint32_t* d_flags, uint32_t* d_any, hipStream_t st) {
+    if (!n) return 0;
+    hipLaunchKernelGGL(k_rlc_seg_flags, dim3(nblocks(n, 256)), dim3(256), 0, st, n, segsh, d_flags, d_any);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// cck_rlc_reduce stopped at the level that has nseg elements (the tree is pairwise with the tail kept
+// alone, so element s of that level is the product of the Miller values [s 2^k, (s + 1) 2^k)): n must
+// halve down to nseg exactly.  Writes the product and flag words of nseg partials (d_any: nseg words).
+int cck_rlc_reduce_seg(size_t n, size_t nseg, uint32_t* d_a, uint32_t* d_b, const uint32_t* d_any, uint32_t force,
+                       uint32_t* d_partials, hipStream_t st) {
+    if (!n || !nseg || nseg > n) return -1;
+    for (size_t m = n; m != nseg; m = (m + 1) / 2)
+        if (m < nseg) return -1;
+    uint32_t *src = d_a, *dst = d_b;
+    while (n > nseg) {
+        reduce_level(n, src, dst, st);
+        n = (n + 1) / 2;
+        uint32_t* t = src;
+        src = dst;
+        dst = t;
+    }
+    hipLaunchKernelGGL(k_rlc_partial_out_seg, dim3((unsigned)nseg), dim3(192), 0, st, nseg, src, d_any, force,
+                       d_partials);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// the per-partial finish's inputs: every partial's 16 window pairs (d_prep a 16 k-element prep SoA,
+// d_flags2 16 k words, as cck_rlc_gather) and its own fall-back flag (d_flags: k words)
+int cck_rlc_gather_each(int mode, size_t k, const uint32_t* d_parts, const uint32_t* d_pw, const uint8_t* d_finf,
+                        uint32_t* d_prep, uint32_t* d_flags2, uint32_t* d_flags, hipStream_t st) {
+    if (!k) return -1;
+    if (mode == 0)
+        hipLaunchKernelGGL((k_rlc_gather<0, true>), dim3((unsigned)k), dim3(256), 0, st, k, d_parts, d_pw, d_finf,
+                           (uint32_t*)nullptr, (size_t)0, d_prep, d_flags2, d_flags);
+    else
+        hipLaunchKernelGGL((k_rlc_gather<1, true>), dim3((unsigned)k), dim3(256), 0, st, k, d_parts, d_pw, d_finf,
+                           (uint32_t*)nullptr, (size_t)0, d_prep, d_flags2, d_flags);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// the per-partial products: d_w holds the 16 k window values (SoA stride 16 k, partial r's at 16 r .. 16 r +
+// 15, tree-aligned), reduced by four pairwise levels (ping-pong with d_t, 8 k elements) to one value a
+// partial, then times the partial's own Miller product: k values in d_t, SoA stride k
+int cck_rlc_each_products(size_t k, uint32_t* d_w, uint32_t* d_t, const uint32_t* d_parts, hipStream_t st) {
+    if (!k) return -1;
+    uint32_t *src = d_w, *dst = d_t;
+    for (size_t n = RLC_WINDOWS * k; n > k; n /= 2) {
+        reduce_level(n, src, dst, st);
+        uint32_t* t = src;
+        src = dst;
+        dst = t;
+    }
+    static_assert(RLC_WINDOWS == 16, "four levels: the k products end in d_w");
+    hipLaunchKernelGGL(k_f12_mul_part, dim3(nblocks(2 * k, 256)), dim3(256), 0, st, k, src, d_parts, dst);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

@@ -186,6 +186,53 @@ cc_status cc_rlc_partial_device(cc_ctx* ctx, size_t n, size_t q, uint64_t base_i
 cc_status cc_rlc_finish_device(cc_ctx* ctx, size_t nparts, const uint32_t* d_partials, uint8_t* d_accept,
                                uint8_t* d_gt_or_null, void* stream);
 
+/* RLC locate: the batch is checked in segments, and only the segments whose own RLC check fails are
+ * verified per credential, so a bad credential costs its segment's re-verification, not the batch's
+ * (rlc = 1 above falls back over the WHOLE batch).  Every segment is an RLC check of its own with
+ * independent deltas, so the 2^-127 bound holds per segment; verdicts always equal rlc = 0's.  Shared
+ * verkey only; no GT output; these calls take no concurrency slot (cc_set_concurrency): like every
+ * other entry point they wait for the slots' batches and are ordered on the context's stream.
+ *   cc_rlc_partial_seg_device : cc_rlc_partial_device in one pass for every segment of `seg`
+ *                               credentials: S = ceil(n / seg) partials (S x CC_RLC_PARTIAL_WORDS u32),
+ *                               partial s covering credentials [s seg, min(n, (s + 1) seg)) and equal to
+ *                               what cc_rlc_partial_device(hi - lo, base_index + s seg, seed32, slice)
+ *                               writes.  seg: a power of two, 4 <= seg <= CC_MAX_BATCH, and S <=
+ *                               CC_MAX_PARTS, else CC_ERR_DECODE; n = 0: CC_OK, nothing written; the other
+ *                               errors as cc_rlc_partial_device.
+ *   cc_rlc_finish_each_device : cc_rlc_finish_device(1, partial s) for every one of nparts partials in
+ *                               one launch sequence: d_accept nparts bytes, d_gt_or_null nparts x 576 B.
+ *                               Takes any partials of the layout (segment, shard or neutral ones); its
+ *                               buffers and ordering are cc_rlc_finish_device's (finishes of either kind
+ *                               run in call order; a cc_set_verkey waits for them).
+ *   cc_verify_batch_locate_device : the segmented partial, the per-partial finish, then ONE per-credential
+ *                               launch sequence over the rejected segments only (their rows compacted;
+ *                               every segment rejected: the batch verified in place); d_verdicts n bytes.
+ *                               seg = 0: the library's default for the context's group mode
+ *                               (CC_LOCATE_SEG_DEFAULT_G2 / _G1).  The call downloads the S accept bytes
+ *                               to decide what to launch, so it SYNCHRONISES `stream` ONCE; the recheck is
+ *                               left queued (synchronise before reading verdicts).  stats3_or_null: three
+ *                               HOST words written before the call returns: segments, rejected segments,
+ *                               credentials rechecked.
+ *   cc_verify_batch_locate    : the host form (host arrays, a fresh seed as rlc = 1 draws it); on a device
+ *                               set every device locates inside its own shard and there is no collective.
+ * The defaults come from tools/bench_rlc_locate.py on config 3's per-GPU shape (131,072 credentials, q =
+ * 16, one MI355X): per mode the segment length with the best one-bad-credential rate among those whose
+ * all-valid rate stays within twice the run's spread of cc_rlc_partial_device + cc_rlc_finish_device's
+ * (SigG2 4,096: 0.6 % below; SigG1 1,024: 3.0 % below).  DESIGN.md "RLC locate" has the table. */
+#define CC_LOCATE_SEG_DEFAULT_G2 4096
+#define CC_LOCATE_SEG_DEFAULT_G1 1024
+cc_status cc_rlc_partial_seg_device(cc_ctx* ctx, size_t n, size_t q, size_t seg, uint64_t base_index,
+                                    const uint8_t* seed32, const uint8_t* d_sigma1, const uint8_t* d_sigma2,
+                                    const uint8_t* d_msgs, uint32_t* d_partials, void* stream);
+cc_status cc_rlc_finish_each_device(cc_ctx* ctx, size_t nparts, const uint32_t* d_partials, uint8_t* d_accept,
+                                    uint8_t* d_gt_or_null, void* stream);
+cc_status cc_verify_batch_locate_device(cc_ctx* ctx, size_t n, size_t q, size_t seg, const uint8_t* seed32,
+                                        const uint8_t* d_sigma1, const uint8_t* d_sigma2, const uint8_t* d_msgs,
+                                        uint8_t* d_verdicts, uint32_t* stats3_or_null, void* stream);
+cc_status cc_verify_batch_locate(cc_ctx* ctx, size_t n, size_t q, size_t seg, const uint8_t* sigma1,
+                                 const uint8_t* sigma2, const uint8_t* msgs, uint8_t* verdicts,
+                                 uint32_t* stats3_or_null);
+
 /* Batch Signature::aggregate: n independent aggregations of `len` (id, Signature) entries each;
  * only the first t entries are used, sigma_1 comes from entry 0, Lagrange over the de-duplicated
  * id set (signature.rs:448-470).  ids: n x len; sigma1/sigma2: n x len encodings;

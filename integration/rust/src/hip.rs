@@ -48,6 +48,18 @@ extern "C" {
                                  d_partial: *mut u32, stream: *mut c_void) -> c_int;
     pub fn cc_rlc_finish_device(ctx: *mut CcCtx, nparts: usize, d_partials: *const u32, d_accept: *mut u8,
                                 d_gt: *mut u8, stream: *mut c_void) -> c_int;
+    // RLC locate: one partial per segment, one accept byte per partial, and the drivers that verify per
+    // credential only the rejected segments (stats3: segments, rejected segments, credentials rechecked)
+    pub fn cc_rlc_partial_seg_device(ctx: *mut CcCtx, n: usize, q: usize, seg: usize, base_index: u64,
+                                     seed32: *const u8, d_sigma1: *const u8, d_sigma2: *const u8,
+                                     d_msgs: *const u8, d_partials: *mut u32, stream: *mut c_void) -> c_int;
+    pub fn cc_rlc_finish_each_device(ctx: *mut CcCtx, nparts: usize, d_partials: *const u32, d_accept: *mut u8,
+                                     d_gt: *mut u8, stream: *mut c_void) -> c_int;
+    pub fn cc_verify_batch_locate_device(ctx: *mut CcCtx, n: usize, q: usize, seg: usize, seed32: *const u8,
+                                         d_sigma1: *const u8, d_sigma2: *const u8, d_msgs: *const u8,
+                                         d_verdicts: *mut u8, stats3: *mut u32, stream: *mut c_void) -> c_int;
+    pub fn cc_verify_batch_locate(ctx: *mut CcCtx, n: usize, q: usize, seg: usize, sigma1: *const u8,
+                                  sigma2: *const u8, msgs: *const u8, verdicts: *mut u8, stats3: *mut u32) -> c_int;
     // Signature::aggregate (signature.rs:448-470), Verkey::aggregate (signature.rs:483-526)
     pub fn cc_signature_aggregate_batch(ctx: *mut CcCtx, n: usize, len: usize, t: usize, ids: *const u64,
                                         sigma1: *const u8, sigma2: *const u8, out1: *mut u8, out2: *mut u8) -> c_int;
