@@ -95,6 +95,15 @@ def test_verify_edge_cases_every_table_width(oc, mode, bits, key):
         # the RLC form reads the same tables (delta-MSM and fold points)
         vr = verify_batch(ctx, n, q, b["s1"], b["s2"], b["msgs"], rlc=True)
         assert [int(x) for x in vr] == want_v, (tag, [nm for nm, a, e in zip(b["names"], vr, want_v) if a != e])
+        # ... and accepts the valid ones on its own (fixed seed): above, a rejected batch falls back to the
+        # per-credential path, which gives these verdicts whatever the RLC check computed.  K1's X~ is the
+        # identity, which the RLC mode does not count as a subgroup point (capi_ctx.cpp refresh_vk_subgroup):
+        # under that verkey it never accepts
+        from test_gpu_rlc_fold_direct import rlc_engine_accepts
+        ok = [i for i in range(n) if want_v[i]]
+        pick = lambda x, item: b"".join(x[i * item:(i + 1) * item] for i in ok)  # noqa: E731
+        assert ok and rlc_engine_accepts(ctx, len(ok), q, pick(b["s1"], sb), pick(b["s2"], sb),
+                                         pick(b["msgs"], q * 48)) is (vk["x"] != 0), tag
     finally:
         ctx.close()
 

@@ -201,6 +201,11 @@ def test_verify_rlc_accept_and_fallback(ctxs, mode):
     for idx in VERIFY_ACCEPT + VERIFY_MIXED:  # the whole-batch check accepts / rejects and falls back
         cr = [d["creds"][i] for i in idx]
         assert list(_verify(ctx, d, cr, rlc=True)) == [c["verdict"] for c in cr], idx
+    from test_gpu_rlc_fold_direct import rlc_engine_accepts
+    for idx in VERIFY_ACCEPT:  # the RLC check itself accepts them (fixed seed, no fallback behind it)
+        cr = [d["creds"][i] for i in idx]
+        assert rlc_engine_accepts(ctx, len(cr), d["q"], _cat(c["sigma1"] for c in cr), _cat(c["sigma2"] for c in cr),
+                                  _cat(m for c in cr for m in c["msgs"])) is True, idx
     # the plain form right behind the RLC's two sequences, on the same staging buffers
     cr = d["creds"][:3]
     v, gts = _verify(ctx, d, cr, want_gt=True)

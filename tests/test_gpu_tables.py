@@ -56,6 +56,11 @@ def test_verkey_table_widths_verify_golden(name, bits):
         vr = verify_batch(ctx, len(cr), d["q"], _cat(c["sigma1"] for c in cr), _cat(c["sigma2"] for c in cr),
                           _cat(m for c in cr for m in c["msgs"]), rlc=True)
         assert [int(x) for x in vr] == [c["verdict"] for c in cr]
+        # ... and accepts the valid credentials on its own (fixed seed, no per-credential fallback behind it)
+        from test_gpu_rlc_fold_direct import rlc_engine_accepts
+        ok = [c for c in cr if c["verdict"] == 1]
+        assert rlc_engine_accepts(ctx, len(ok), d["q"], _cat(c["sigma1"] for c in ok), _cat(c["sigma2"] for c in ok),
+                                  _cat(m for c in ok for m in c["msgs"])) is True
     finally:
         ctx.close()
 
