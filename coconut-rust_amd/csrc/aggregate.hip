@@ -62,7 +62,7 @@ DEV void ld_aff_aos(Aff<F>& a, const uint32_t* p) {
 // - The numerator is shared: with P = the product of the credential's distinct ids, l_i =
 //   P / (x_i den_i), so a task multiplies only its t - 1 differences (P is formed once per
 //   credential a lane touches; a credential holding the id 0 takes the per-task numerator instead).
-// - The tasks' denominators share ONE Fermat inversion (Montgomery's trick: with
+// - The tasks' denominators share ONE inversion, the divstep fm_inv of fr.h (Montgomery's trick: with
 //   P_q = den_0 ... den_{q-1}, l_q = (num_q P_q) / P_{q+1}, walking q down from 1 / P_cnt and
 //   multiplying den_q back in).
 // - The O(t^2) duplicate scan (HashSet semantics) runs once per credential a lane touches; a
@@ -1146,7 +1146,8 @@ int cck_lagrange(size_t n, size_t len, size_t t, const uint64_t* d_ids, uint32_t
     constexpr int lt = 2;  // tasks per lane: with the divstep inversion 1.82 / 2.01 ms for 2 / 4 at config 4
                            // (the Fermat ladder measured 3.96 / 3.62 / 4.10 for 2 / 4 / 8)
     // ids of the credentials one block's 64 x lt tasks touch: at most 64 lt / t + 2 rows of t; past
-    // 64 KiB (t > 3,968) the ids are read from global memory
+    // 64 KiB (lt = 2: t > 4,032, where the request is exactly 65,536 bytes) the ids are read from global
+    // memory
     const size_t lds = (64 * (size_t)lt + 2 * t) * 8;
     const unsigned nb = nblocks((n * t + lt - 1) / lt, 64);
     if (lds <= 64 * 1024)

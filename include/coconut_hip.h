@@ -657,6 +657,20 @@ cc_status cc_set_timing(cc_ctx* ctx, int enabled);
 int cc_selftest_lazy(int op, size_t n, const int32_t* a, const int32_t* b, const int32_t* c, const int32_t* d,
                      int32_t* out);
 
+/* Device self-test of the canonical 12 x 32 Fp every non-pairing kernel uses (csrc/field.h, with the
+ * out-of-line product), of its Fp2 helpers and of the scalar field (csrc/fr.h, csrc/codec.h), one row
+ * per lane on n rows of 12 words (host arrays; unused high words zero; b may be NULL for a one-operand
+ * op).  Fp ops, raw rows in and out: 0 fp_add, 1 fp_sub, 2 fp_neg, 3 fp_dbl, 4 fp_mul and 5 fp_sqr
+ * (a b / 2^406 mod p on the rows as given), 6 fp_to_mont, 7 fp_from_mont, 8 fp_raw_reduce (a < 2^384),
+ * 9 fp_inv (Montgomery form in and out).  Fp2 ops, row i of a the real and row i of b the imaginary
+ * half of one operand, out holding 2n rows (real halves, then imaginary halves): 10 f2_mul (by row
+ * (i + 1) mod n), 11 f2_sqr, 12 f2_inv, 13 f2_mul_xi.  Fr ops on words 0..7: 14 fm_mul_v, 15 fm_sub,
+ * 16 fm_reduce_once (a = a raw sum below 2r), 17 fm_from_u64 (words 0..1), 18 fm_to_canon,
+ * 19 fr_mul_canon, 20 fr_inv_int, 21 fm_inv, 22 rlc_delta_abs (magnitude in words 0..7, sign in word
+ * 8), 23 fr_from_be48 (the row read as 48 big-endian bytes).  Test infrastructure, as above.  Returns 0,
+ * or -1 on a HIP error or an unknown op. */
+int cc_selftest_field(int op, size_t n, const uint32_t* a, const uint32_t* b, uint32_t* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -197,6 +197,8 @@ extern "C" {
     // device self-test of the lazy field core (test infrastructure; no context)
     pub fn cc_selftest_lazy(op: c_int, n: usize, a: *const i32, b: *const i32, c: *const i32, d: *const i32,
                             out: *mut i32) -> c_int;
+    // device self-test of the canonical Fp, Fp2 and Fr arithmetic (test infrastructure; no context)
+    pub fn cc_selftest_field(op: c_int, n: usize, a: *const u32, b: *const u32, out: *mut u32) -> c_int;
 }
 
 /// Owner of one `cc_ctx` (one per calling thread: the C ABI's threading contract).

@@ -214,7 +214,8 @@ def test_large_verkey_falls_back_to_8_bits_and_failed_build_leaves_no_verkey():
 
 
 def test_lagrange_large_threshold_global_ids():
-    """t = 4,000 (> 3,968: k_lagrange reads the ids from global memory).  Shares of a degree-2
+    """t = 4,000 (with two tasks a lane k_lagrange still stages these ids in LDS: the switch to global
+    memory is above t = 4,032, and tests/test_gpu_lagrange_direct.py runs either side of it).  Shares of a degree-2
     polynomial f (exact for any t >= 3 points): sigma_2,i = k f(i) G, X~_i = f(i) g~; both aggregates
     must equal the master values k f(0) G and f(0) g~."""
     import coconut
