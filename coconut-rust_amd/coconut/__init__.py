@@ -18,7 +18,8 @@ from .dist import DeviceEngine, PokDeviceEngine  # noqa: F401
 from .issuance import (blind_sign_batch, sigreq_verify_batch, vss_verify_batch, unblind_batch,  # noqa: F401
                        SignatureRequest, SignatureRequestPoK, sigreq_new_batch, sigreq_pok_init_batch,
                        sigreq_pok_gen_proof_batch, sigreq_pok_to_bytes_batch, sigreq_challenge_batch,
-                       sigreq_proof_bytes, sigreq_verify_batch_device, blind_sign_batch_device)
+                       sigreq_proof_bytes, sigreq_verify_batch_device, blind_sign_batch_device,
+                       vss_verify_sets, vss_verify_sets_device)
 from .keygen import (Signer, Sigkey, keygen_deal_batch, keygen_combine_batch,  # noqa: F401
-                     keygen_deal_batch_device, keygen_combine_batch_device,
+                     keygen_deal_batch_device, keygen_combine_batch_device, keygen_verify_shares_device,
                      trusted_party_SSS_keygen, trusted_party_PVSS_keygen)

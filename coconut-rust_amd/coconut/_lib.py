@@ -94,6 +94,10 @@ _SIGS = {
     "cc_keygen_combine_batch_device": (c_int, [c_p, c_sz, c_sz, c_sz, c_sz, c_sz, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
                                                c_p, c_p, c_p, c_p, c_p, c_p]),
     "cc_vss_verify_batch": (c_int, [c_p, c_sz, c_sz, c_p, c_p, c_p, c_sz, c_p, c_p, c_p, c_p]),
+    "cc_vss_verify_sets": (c_int, [c_p, c_sz, c_sz, c_sz, c_p, c_p, c_p, c_p, c_int, c_p, c_p]),
+    "cc_vss_verify_sets_device": (c_int, [c_p, c_sz, c_sz, c_sz, c_p, c_p, c_p, c_p, c_int, c_p, c_p, c_p, c_p]),
+    "cc_keygen_verify_shares_batch_device": (c_int, [c_p, c_sz, c_sz, c_sz, c_sz, c_p, c_p, c_p, c_p, c_p, c_int, c_p,
+                                                     c_p, c_p, c_p]),
     "cc_fixed_base_mul": (c_int, [c_p, c_int, c_p, c_sz, c_p, c_p]),
     "cc_rlc_partial_words": (c_int, []),
     "cc_rlc_partial_device": (c_int, [c_p, c_sz, c_sz, ctypes.c_uint64, c_p, c_p, c_p, c_p, c_p, c_p]),

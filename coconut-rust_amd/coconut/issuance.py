@@ -156,6 +156,63 @@ def vss_verify_batch(ctx: Context, t: int, g: bytes, h: bytes, commitment_sets: 
     return v[:n]
 
 
+def _set_begin(set_begin, n_sets: int, n: int) -> np.ndarray:
+    """The CSR offsets as the C ABI reads them: n_sets + 1 uint64 on the host."""
+    sb = np.ascontiguousarray(np.asarray(set_begin, dtype=np.uint64))
+    if len(sb) != n_sets + 1:
+        raise CoconutError(-4, f"set_begin: {len(sb)} entries for {n_sets} sets ({n} rows)")
+    return sb
+
+
+def vss_verify_sets(ctx: Context, t: int, commitment_sets: Sequence[Sequence[bytes]], set_begin: Sequence[int],
+                    ids: Sequence[int], shares: Sequence[tuple], rlc: bool = False, want_stats: bool = False):
+    """PedersenVSS::verify_share for the shares of whole commitment sets, under the g, h bound by
+    Context.set_keygen_params (cc_vss_verify_sets): rows [set_begin[j], set_begin[j + 1]) belong to
+    commitment_sets[j].  rlc: one random-linear-combination check a set first, per share only where it fails.
+    Returns the verdicts, or (verdicts, stats) with want_stats: stats = (sets, sets the RLC check rejected,
+    irregular sets, shares verified per share)."""
+    n, ns = len(ids), len(commitment_sets)
+    cm = b"".join(c for cs in commitment_sets for c in cs)
+    sb = _set_begin(set_begin, ns, n)
+    iv = np.ascontiguousarray(np.asarray(ids, dtype=np.uint64))
+    sh = b"".join(a + b for a, b in shares)
+    need(cm, ns * t * 97, "commitments")
+    need(sh, n * 96, "shares")
+    keep = [buf(cm), buf(sh)]
+    v = np.zeros(max(n, 1), dtype=np.uint8)
+    st = np.zeros(4, dtype=np.uint32)
+    check(lib.cc_vss_verify_sets(ctx.h, n, t, ns, ctypes.c_void_p(sb.ctypes.data), keep[0][0],
+                                 ctypes.c_void_p(iv.ctypes.data), keep[1][0], 1 if rlc else 0,
+                                 ctypes.c_void_p(v.ctypes.data), ctypes.c_void_p(st.ctypes.data)),
+          "cc_vss_verify_sets")
+    return (v[:n], tuple(int(x) for x in st)) if want_stats else v[:n]
+
+
+def vss_verify_sets_device(ctx: Context, n: int, t: int, n_sets: int, set_begin: Sequence[int], commitments, ids,
+                           shares, rlc: bool = False, seed: Optional[bytes] = None, stream=None):
+    """vss_verify_sets on CUDA tensors (cc_vss_verify_sets_device): commitments n_sets x t x 97 and shares
+    n x (s | s') as torch.uint8, ids as a torch.int64 / uint64 tensor of n entries; set_begin stays on the host.
+    seed: 32 bytes keying the deltas (None with rlc: drawn here).  The call synchronises `stream` once.
+    Returns (verdict tensor, stats)."""
+    import torch
+    sb = _set_begin(set_begin, n_sets, n)
+    _dev_need(((commitments, n_sets * t * 97 if n else 0, "commitments"), (shares, n * 96, "shares")))
+    if n and (ids is None or ids.element_size() != 8 or ids.numel() < n or not ids.is_contiguous() or not ids.is_cuda):
+        raise CoconutError(-4, "ids: a contiguous device tensor of n 64-bit entries is required")
+    if rlc and seed is None:
+        seed = secrets.token_bytes(32)
+    if seed is not None:
+        need(seed, 32, "seed")
+    keep = buf(bytes(seed)) if seed is not None else (None, None)
+    v = torch.empty(n, dtype=torch.uint8, device=shares.device if n else None)
+    st = np.zeros(4, dtype=np.uint32)
+    check(lib.cc_vss_verify_sets_device(ctx.h, n, t, n_sets, ctypes.c_void_p(sb.ctypes.data), _dev_ptr(commitments),
+                                        _dev_ptr(ids), _dev_ptr(shares), 1 if rlc else 0, keep[0], _dev_ptr(v),
+                                        ctypes.c_void_p(st.ctypes.data), _stream_ptr(stream)),
+          "cc_vss_verify_sets_device")
+    return v, tuple(int(x) for x in st)
+
+
 def unblind_batch(ctx: Context, c1s: Sequence[bytes], c2s: Sequence[bytes], sks: Sequence[bytes]) -> List[bytes]:
     """BlindSignature::unblind per row: sigma_2 = c~2 - sk * c~1 with that row's ElGamal secret key
     (48 B big-endian); sigma_1 is the blind signature's h."""

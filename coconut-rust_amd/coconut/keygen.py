@@ -5,6 +5,7 @@ cc_keygen_combine_batch).  The polynomials are the caller's, or drawn here from 
 from __future__ import annotations
 
 import ctypes
+import secrets
 from dataclasses import dataclass
 from typing import List, Optional
 
@@ -117,6 +118,33 @@ def keygen_combine_batch_device(ctx: Context, m: int, d: int, q: int, t: int, to
                                              *[_dev_ptr(o) for o in outs], _stream_ptr(stream)),
           "cc_keygen_combine_batch_device")
     return tuple(outs)
+
+
+def keygen_verify_shares_device(ctx: Context, m: int, q: int, t: int, total: int, x, y, xt, yt, comm,
+                                rlc: bool = False, seed: Optional[bytes] = None, stream=None):
+    """PedersenVSS::verify_share for every share of m keygens, read in place from the tensors
+    keygen_deal_batch_device / keygen_combine_batch_device returned (cc_keygen_verify_shares_batch_device).
+    Verdict (keygen (q + 1) + p) total + signer belongs to polynomial p (0: x, 1 + j: y_j) and signer index
+    0 .. total - 1.  rlc: one random-linear-combination check a (keygen, polynomial) first, keyed by `seed` (32
+    bytes; None: drawn here).  The call synchronises `stream` once.  Returns (verdict tensor, stats) with
+    stats = (sets, sets the RLC check rejected, irregular sets, shares verified per share)."""
+    import torch
+    sx, sy, _, _, sc, _, _ = _sizes(ctx, m, q, t, total)
+    _dev_need(((x, sx, "x shares"), (y, sy, "y shares"), (xt, sx, "x blinding shares"),
+               (yt, sy, "y blinding shares"), (comm, sc, "commitments")))
+    if rlc and seed is None:
+        seed = secrets.token_bytes(32)
+    if seed is not None:
+        need(seed, 32, "seed")
+    keep = buf(bytes(seed)) if seed is not None else (None, None)
+    n = m * (q + 1) * total
+    v = torch.empty(n, dtype=torch.uint8, device=x.device if n else None)
+    st = np.zeros(4, dtype=np.uint32)
+    check(lib.cc_keygen_verify_shares_batch_device(ctx.h, m, q, t, total, *[_dev_ptr(a) for a in (x, y, xt, yt, comm)],
+                                                   1 if rlc else 0, keep[0], _dev_ptr(v),
+                                                   ctypes.c_void_p(st.ctypes.data), _stream_ptr(stream)),
+          "cc_keygen_verify_shares_batch_device")
+    return v, tuple(int(s) for s in st)
 
 
 def _signers(ctx: Context, q: int, total: int, x: bytes, y: bytes, X: bytes, Y: bytes) -> List[Signer]:

@@ -50,6 +50,8 @@ cc_status cc_set_keygen_params(cc_ctx* c, const uint8_t* g_tilde, const uint8_t*
         memcpy(enc + 97, vss_h, 97);
         s = decode_points_host(c, 1, 2, enc, c->kg_gh_aff.as<uint32_t>(), c->kg_gh_inf.as<uint32_t>());
         if (s) return s;
+        if (c->kg_gh_enc.ensure(2 * 97)) return CC_ERR_HIP;
+        KCK(HipMem::h2d(c->kg_gh_enc.p, enc, 2 * 97, c->stream));  // synchronised below
         KCK(cck_build_table(1, 2, wb, c->kg_gh_aff.as<uint32_t>(), c->kg_gh_inf.as<uint32_t>(), pw.as<uint32_t>(),
                             c->kg_gh_table.as<uint32_t>(), 1, c->stream));
         HIPCK(hipStreamSynchronize(c->stream));

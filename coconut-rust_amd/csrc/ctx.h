@@ -1,6 +1,6 @@
 // Internal header of the C ABI's host side (include/coconut_hip.h), which lives in the capi_*.cpp files, one
 // per area: capi_ctx (contexts, tables, timing, concurrency), capi_verify (Signature::verify, the RLC,
-// device sets), capi_pok, capi_aggregate, capi_issuer, capi_holder, capi_keygen.  Here: the HIP policies of
+// device sets), capi_pok, capi_aggregate, capi_issuer, capi_holder, capi_keygen, capi_vss.  Here: the HIP policies of
 // devbuf.h and slots.h, struct cc_ctx, the stream-ordering helpers, and the helpers more than one area
 // calls.  The cc_* definitions take their C linkage from coconut_hip.h's declarations.  Every compute step
 // runs in the HIP kernels behind launch.h — there is no CPU fallback in this library.
@@ -170,6 +170,10 @@ struct cc_ctx {
     bool have_kg = false, kg_have_gh = false;
     int kg_wbits = 8;
     DevBuf kg_gt_aff, kg_gt_inf, kg_gt_table, kg_gh_aff, kg_gh_inf, kg_gh_table, kg_io[14];
+    // verify_share over commitment sets (capi_vss.cpp, vss.hip): g | h as given (the irregular sets' exact route
+    // and the G1 test read the encodings), and the drivers' workspaces and plan (VssBuf)
+    DevBuf kg_gh_enc, vss[20];
+    std::vector<uint64_t> vss_plan;
     int n_simd = 0;  // SIMDs of the device (4 a CU), read once (pok_rlc_twin)
     // issuer table (cc_set_issuers): sorted ids, decoded verkeys, per-base 8-bit window tables
     size_t iss_n = 0, iss_q = 0;

@@ -153,6 +153,37 @@ int cck_kg_commit(size_t n, const uint8_t* d_cf, const uint8_t* d_ct, const uint
 int cck_kg_derive(int group, size_t nrow, int q, const uint8_t* d_x, const uint8_t* d_y, const uint32_t* d_table,
                   int wbits, const uint32_t* d_binf, uint8_t* d_X, uint8_t* d_Y, hipStream_t st);
 int cck_kg_sum(int g1, size_t m, size_t inner, int d, const uint8_t* d_in, uint8_t* d_out, hipStream_t st);
+// Pedersen VSS verify_share over commitment sets (vss.hip).  How a launch finds its rows: the CSR form
+// (set_begin non-NULL: set j holds rows [set_begin[j], set_begin[j + 1]) of ids / shares), or the keygen
+// outputs in place (set_begin NULL: set j = keygen (q + 1) + p holds signers 1 .. total, rows
+// [j total, (j + 1) total), shares at keygen.hip's kg_share_off in x / y and xt / yt).  Device pointers.
+struct cck_vss_rows {
+    const uint64_t* set_begin;
+    const uint64_t* ids;
+    const uint8_t* shares;
+    const uint8_t *x, *y, *xt, *yt;
+    uint32_t q, total;
+};
+size_t cck_vss_prep_words(size_t npts);
+size_t cck_vss_msm_words(size_t t);
+int cck_vss_prep(size_t npts, int t, const uint8_t* d_comms, const uint8_t* d_gh, uint32_t* d_prep, uint32_t* d_set_flag,
+                 uint32_t* d_gh_flag, uint8_t* d_gh_neg, hipStream_t st);
+int cck_vss_exact(size_t nrow, int t, const cck_vss_rows* rows, const uint32_t* d_sel_set, const uint64_t* d_sel_off,
+                  size_t nsel, const uint32_t* d_prep, const uint32_t* d_table, int wbits, const uint32_t* d_binf,
+                  uint8_t* d_verdicts, hipStream_t st);
+int cck_vss_scalars(size_t n_sets, int t, const cck_vss_rows* rows, const uint32_t* d_key, uint32_t* d_A, uint32_t* d_UU,
+                    hipStream_t st);
+int cck_vss_msm(size_t j0, size_t cnt, int t, const uint8_t* d_comms, const uint32_t* d_A, const uint32_t* d_UU,
+                const uint32_t* d_table, int wbits, const uint32_t* d_binf, const uint32_t* d_set_flag,
+                const uint32_t* d_gh_flag, uint32_t* d_scratch, uint8_t* d_status, hipStream_t st);
+int cck_vss_status(size_t n_sets, const uint32_t* d_set_flag, const uint32_t* d_gh_flag, uint8_t* d_status,
+                   hipStream_t st);
+int cck_vss_fill(size_t n, size_t n_sets, const cck_vss_rows* rows, const uint8_t* d_status, uint8_t* d_verdicts,
+                 hipStream_t st);
+int cck_vss_gather(size_t nrow, const cck_vss_rows* rows, const uint32_t* d_sel_set, const uint64_t* d_sel_off,
+                   size_t nsel, uint32_t* d_set_of, uint64_t* d_ids, uint8_t* d_shares, uint64_t* d_row_of,
+                   hipStream_t st);
+int cck_vss_scatter(size_t nrow, const uint64_t* d_row_of, const uint8_t* d_ok, uint8_t* d_verdicts, hipStream_t st);
 int cck_rlc_partial_words();
 int cck_fexp_q(size_t n, const uint32_t* d_f, const uint32_t* d_flags, uint8_t* d_verdicts, uint8_t* d_gt,
                hipStream_t st);

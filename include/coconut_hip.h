@@ -636,6 +636,64 @@ cc_status cc_keygen_combine_batch_device(cc_ctx* ctx, size_t m, size_t d, size_t
                                          uint8_t* d_out_y, uint8_t* d_out_xt, uint8_t* d_out_yt,
                                          uint8_t* d_out_comm, uint8_t* d_out_X, uint8_t* d_out_Y, void* stream);
 
+/* Pedersen VSS verify_share over commitment SETS (the consumer of the deal and the combine: every
+ * participant of the decentralized keygen checks every share it receives, keygen.rs:141-157, 334-349).  g and
+ * h are the ones bound by cc_set_keygen_params, with its [g, h] table.  Shares of set j are rows
+ * [set_begin[j], set_begin[j + 1]) of ids / shares (set_begin: HOST, n_sets + 1 entries; empty sets allowed)
+ * and are checked against commitments[j] (t x 97 B).
+ *   cc_vss_verify_sets_device : device buffers; rlc = 0: every verdict is the reference's, and equals
+ *                               cc_vss_verify_batch's on the same shares whenever g and h lie in G1 or are
+ *                               skipped (for a g or h outside G1 that call's (r - s) g is not -(s g)).  Sets whose decodable points (g and h included) all lie in G1
+ *                               take one lane a share: Horner with the 64-bit id as a plain integer over
+ *                               the set's commitments, decoded once a set, and two table lookups for
+ *                               s g + s' h.  A set holding a decodable point outside G1 is IRREGULAR (the
+ *                               reference's verdict there depends on id^k mod r): its rows run through
+ *                               cc_vss_verify_batch's kernel unchanged, handed -g, -h and r - s, r - s'.
+ *                               rlc != 0: every regular set is first checked as ONE (t + 2)-term MSM,
+ *                               sum_k A_k C_k - U g - U' h == O with A_k = sum_i delta_i id_i^k, U = sum
+ *                               delta_i s_i, U' = sum delta_i s'_i and the 128-bit delta_i of the RLC batch
+ *                               mode keyed by seed32 (HOST, 32 B) and the row index; an accepted set's
+ *                               verdicts are 1, a rejected set is re-verified per share, so the verdicts
+ *                               are rlc = 0's except that a set holding an invalid share is accepted with
+ *                               probability <= 2^-127.  Every set is a check of its own.
+ *                               The driver reads one status byte a set to decide what to launch: it
+ *                               SYNCHRONISES `stream` once (as cc_verify_batch_locate_device).
+ *                               stats4 (HOST, may be NULL): sets, sets the RLC check rejected, irregular
+ *                               sets, shares verified per share.
+ *   cc_vss_verify_sets        : the same over host buffers, on the context stream; rlc != 0 draws a fresh
+ *                               seed.
+ *   cc_keygen_verify_shares_batch_device : the same kernels over cc_keygen_deal_batch_device's /
+ *                               cc_keygen_combine_batch_device's outputs in place: set (keygen, p) has the
+ *                               commitments d_comm + (keygen (q + 1) + p) t 97 and the shares of signers
+ *                               1 .. total (p = 0: x / xt, p = 1 + j: y_j / yt_j); verdict index
+ *                               (keygen (q + 1) + p) total + signer, which is also the delta's row index.
+ * When rlc pays (one MI355X, tools/bench_vss_verify.py, DESIGN.md "Device keygen: verify_share"): with every
+ * share valid, rlc = 1 took 0.27x the rate of rlc = 0 at five shares a set (t = 3) and 1.40x at a hundred
+ * shares a set (t = 67); the crossing between them was not located.  rlc is for sets of tens of shares and
+ * more, not for sets of a handful; a set it rejects costs its per-share check on top.
+ * Checks, in this order and before the n = 0 shortcut: NULL context, a NULL buffer the call would read or
+ * write with n > 0, NULL set_begin, NULL seed32 with rlc != 0 (device forms): CC_ERR_DECODE; no keygen
+ * params or no g, h bound: CC_ERR_STATE; t = 0 or t > 4096, n, n_sets or n_sets t above CC_MAX_BATCH,
+ * set_begin[0] != 0, set_begin[n_sets] != n, set_begin decreasing somewhere: CC_ERR_DECODE; the keygen-shaped
+ * call: t > total: CC_ERR_THRESHOLD (as the deal), then total > CC_MAX_IDS, q > CC_MAX_Q or a size above
+ * CC_MAX_BATCH: CC_ERR_DECODE; n = 0: CC_OK, nothing launched.
+ * Nothing is rejected that the reference would not reject: scalars are reduced mod r, a commitment that
+ * does not decode is the identity and is skipped, an identity or undecodable g or h is skipped in every sum.
+ * The calls take no concurrency slot: they first wait for the slots' batches and are ordered on the
+ * context's stream.  A device set forwards to its first device. */
+cc_status cc_vss_verify_sets_device(cc_ctx* ctx, size_t n, size_t t, size_t n_sets, const uint64_t* set_begin,
+                                    const uint8_t* d_commitments, const uint64_t* d_ids, const uint8_t* d_shares,
+                                    int rlc, const uint8_t* seed32, uint8_t* d_verdicts, uint32_t* stats4_or_null,
+                                    void* stream);
+cc_status cc_vss_verify_sets(cc_ctx* ctx, size_t n, size_t t, size_t n_sets, const uint64_t* set_begin,
+                             const uint8_t* commitments, const uint64_t* ids, const uint8_t* shares, int rlc,
+                             uint8_t* verdicts, uint32_t* stats4_or_null);
+cc_status cc_keygen_verify_shares_batch_device(cc_ctx* ctx, size_t m, size_t q, size_t t, size_t total,
+                                               const uint8_t* d_x, const uint8_t* d_y, const uint8_t* d_xt,
+                                               const uint8_t* d_yt, const uint8_t* d_comm, int rlc,
+                                               const uint8_t* seed32, uint8_t* d_verdicts, uint32_t* stats4_or_null,
+                                               void* stream);
+
 /* Batch fixed-base scalar multiplication out_i = k_i * base (group 1 = G1, 2 = G2); scalars n x 48 B
  * big-endian Fr, out n encodings.  The keygen derivation g~ * x_i (reference src/keygen.rs:27-32)
  * and the issuer's h^e (src/signature.rs:423-428) in batch form. */

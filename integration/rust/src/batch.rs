@@ -134,6 +134,27 @@ pub fn verify_shares_batch(t: usize, g: &G1, h: &G1, sets: &[Vec<G1>], set_of: &
     v.into_iter().map(|b| b == 1).collect()
 }
 
+/// PedersenVSS::verify_share for the shares of whole commitment sets under the g, h bound by
+/// cc_set_keygen_params: shares[j] are the (id, s, s') received for sets[j].  rlc: one random-linear-combination
+/// check a set first, per share only where it fails.  One Vec<bool> per set.
+pub fn verify_share_sets_batch(t: usize, sets: &[Vec<G1>], shares: &[Vec<(u64, FieldElement, FieldElement)>],
+                               rlc: bool, ctx: &HipCtx) -> Vec<Vec<bool>> {
+    assert!(shares.len() == sets.len(), "one share list per commitment set");  // len-guard
+    assert!(sets.iter().all(|s| s.len() == t), "every commitment set has t points");  // len-guard
+    let mut set_begin: Vec<u64> = vec![0];
+    for s in shares { set_begin.push(set_begin[set_begin.len() - 1] + s.len() as u64); }
+    let n = set_begin[sets.len()] as usize;
+    let cm: Vec<u8> = sets.iter().flatten().flat_map(|c| c.to_bytes()).collect();
+    let ids: Vec<u64> = shares.iter().flatten().map(|s| s.0).collect();
+    let sh: Vec<u8> = shares.iter().flatten().flat_map(|(_, s, st)| [s.to_bytes(), st.to_bytes()].concat()).collect();
+    assert!(cm.len() == sets.len() * t * 97 && sh.len() == n * 96, "encodings");  // len-guard
+    let mut v = vec![0u8; n];
+    ctx.check(unsafe { cc_vss_verify_sets(ctx.raw, n, t, sets.len(), set_begin.as_ptr(), cm.as_ptr(), ids.as_ptr(),
+                                          sh.as_ptr(), rlc as c_int, v.as_mut_ptr(), std::ptr::null_mut()) });
+    (0..sets.len()).map(|j| v[set_begin[j] as usize..set_begin[j + 1] as usize].iter().map(|&b| b == 1).collect())
+        .collect()
+}
+
 impl Verkey {
     /// Batch form of `Verkey::aggregate` (signature.rs:483-526): n aggregations of `len` (id, Verkey)
     /// entries each; only the first `threshold` are used (HashSet semantics of the ids as there).

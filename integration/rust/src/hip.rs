@@ -190,6 +190,20 @@ extern "C" {
                                           d_comm: *const u8, d_out_x: *mut u8, d_out_y: *mut u8, d_out_xt: *mut u8,
                                           d_out_yt: *mut u8, d_out_comm: *mut u8, d_out_x_tilde: *mut u8,
                                           d_out_y_tilde: *mut u8, stream: *mut c_void) -> c_int;
+    // verify_share over commitment sets under the keygen params' g, h: set_begin and seed32 on the host;
+    // rlc != 0 checks every set as one MSM first; the device forms synchronise `stream` once
+    pub fn cc_vss_verify_sets_device(ctx: *mut CcCtx, n: usize, t: usize, n_sets: usize, set_begin: *const u64,
+                                     d_commitments: *const u8, d_ids: *const u64, d_shares: *const u8, rlc: c_int,
+                                     seed32: *const u8, d_verdicts: *mut u8, stats4_or_null: *mut u32,
+                                     stream: *mut c_void) -> c_int;
+    pub fn cc_vss_verify_sets(ctx: *mut CcCtx, n: usize, t: usize, n_sets: usize, set_begin: *const u64,
+                              commitments: *const u8, ids: *const u64, shares: *const u8, rlc: c_int,
+                              verdicts: *mut u8, stats4_or_null: *mut u32) -> c_int;
+    pub fn cc_keygen_verify_shares_batch_device(ctx: *mut CcCtx, m: usize, q: usize, t: usize, total: usize,
+                                                d_x: *const u8, d_y: *const u8, d_xt: *const u8, d_yt: *const u8,
+                                                d_comm: *const u8, rlc: c_int, seed32: *const u8,
+                                                d_verdicts: *mut u8, stats4_or_null: *mut u32,
+                                                stream: *mut c_void) -> c_int;
     pub fn cc_fixed_base_mul(ctx: *mut CcCtx, group: c_int, base: *const u8, n: usize, scalars: *const u8,
                              out: *mut u8) -> c_int;
     pub fn cc_last_timing(ctx: *const CcCtx, prep_ms: *mut f32, miller_ms: *mut f32, fexp_ms: *mut f32) -> c_int;
