@@ -12,7 +12,8 @@ from ._lib import version, source_hash  # noqa: F401
 from .signature import (GroupMode, Params, Verkey, Signature, Context, verify_batch, verify_batch_locate,  # noqa: F401
                         signature_aggregate_batch, verkey_aggregate_batch, verkey_aggregate_ids, fixed_base_mul, subgroup_check, hash_to_curve, hash_msg, params_new,
                         G1_GENERATOR, G2_GENERATOR)
-from .pok_sig import (PoKOfSignature, PoKOfSignatureProof, pok_verify_batch, pok_init_batch,  # noqa: F401
+from .pok_sig import (PoKOfSignature, PoKOfSignatureProof, pok_verify_batch, pok_verify_batch_locate,  # noqa: F401
+                      pok_init_batch,
                       pok_gen_proof_batch, pok_challenge_batch, pok_to_bytes_batch)
 from .dist import DeviceEngine, PokDeviceEngine  # noqa: F401
 from .issuance import (blind_sign_batch, sigreq_verify_batch, vss_verify_batch, unblind_batch,  # noqa: F401

@@ -59,6 +59,12 @@ _SIGS = {
     "cc_pok_rlc_partial_device": (c_int, [c_p, c_sz, c_sz, c_sz, c_sz, ctypes.c_uint64, c_p, c_p, c_p, c_p, c_p,
                                           c_p, c_p, c_p, c_p, c_p, c_p]),
     "cc_pok_verify_batch_rlc": (c_int, [c_p, c_sz, c_sz, c_sz, c_sz, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "cc_pok_rlc_partial_seg_device": (c_int, [c_p, c_sz, c_sz, c_sz, c_sz, c_sz, ctypes.c_uint64, c_p, c_p, c_p, c_p,
+                                              c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "cc_pok_verify_batch_locate_device": (c_int, [c_p, c_sz, c_sz, c_sz, c_sz, c_sz, c_p, c_p, c_p, c_p, c_p, c_p,
+                                                  c_p, c_p, c_p, c_p, c_p, c_p]),
+    "cc_pok_verify_batch_locate": (c_int, [c_p, c_sz, c_sz, c_sz, c_sz, c_sz, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
+                                           c_p, c_p]),
     "cc_pok_init_batch": (c_int, [c_p, c_sz, c_sz, c_sz, c_sz, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
     "cc_pok_init_batch_device": (c_int, [c_p, c_sz, c_sz, c_sz, c_sz, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
                                          c_p]),

@@ -281,6 +281,36 @@ class PokDeviceEngine(DeviceEngine):
         self._leave()
         return self.part
 
+    def partial_seg(self, seg: int):
+        """cc_pok_rlc_partial_seg_device: one partial per segment of `seg` proofs (a power of two >= 4), a
+        (ceil(n / seg), PARTIAL_WORDS) int32 tensor; partial s is what partial() gives for the slice with
+        base_index + s * seg.  finish_each (inherited) decides them."""
+        import torch
+        seed = self.seed if self.seed is not None else os.urandom(32)
+        nseg = -(-self.n // seg) if seg > 0 else 0
+        parts = torch.empty((max(nseg, 1), PARTIAL_WORDS), dtype=torch.int32, device=self.dev)
+        self._enter()
+        self._check(self.lib.cc_pok_rlc_partial_seg_device(self.ctx.h, self.n, self.q, self.r, self.nresp, seg,
+                                                           self.base_index, seed, *self._proof_args(),
+                                                           ctypes.c_void_p(parts.data_ptr()), self._sh),
+                    "cc_pok_rlc_partial_seg_device")
+        self._leave()
+        return parts[:nseg]
+
+    def locate(self, seg: int = 0):
+        """cc_pok_verify_batch_locate_device over the slice (deltas from index 0): (verdicts uint8[n],
+        (segments, rejected segments, proofs rechecked)); seg = 0: the library's default for the mode."""
+        seed = self.seed if self.seed is not None else os.urandom(32)
+        stats = np.zeros(3, dtype=np.uint32)
+        self._enter()
+        self._check(self.lib.cc_pok_verify_batch_locate_device(self.ctx.h, self.n, self.q, self.r, self.nresp, seg,
+                                                               seed, *self._proof_args(),
+                                                               ctypes.c_void_p(self.verdicts.data_ptr()),
+                                                               ctypes.c_void_p(stats.ctypes.data), self._sh),
+                    "cc_pok_verify_batch_locate_device")
+        self._leave()
+        return self.verdicts.cpu().numpy(), tuple(int(x) for x in stats)
+
     def per_credential(self) -> np.ndarray:
         self._enter()
         self._check(self.lib.cc_pok_verify_batch_device(self.ctx.h, self.n, self.q, self.r, self.nresp,

@@ -91,6 +91,30 @@ def pok_verify_batch(ctx: Context, n: int, q: int, revealed_idx, nresp: int, sig
     return verdicts[:n]
 
 
+def pok_verify_batch_locate(ctx: Context, n: int, q: int, revealed_idx, nresp: int, sigma1: bytes, sigma2: bytes,
+                            J: bytes, T: bytes, responses: bytes, chal: bytes, revealed_msgs: bytes, seg: int = 0):
+    """Batch PoK verify through the RLC locate mode (cc_pok_verify_batch_locate; shared verkey): the batch is
+    checked in segments of `seg` proofs (a power of two >= 4; 0: the library's default) and only the rejected
+    segments are verified per proof.  Returns (verdicts uint8[n], stats) with stats = (segments, rejected
+    segments, proofs rechecked); the verdicts equal pok_verify_batch's."""
+    r = len(revealed_idx)
+    sb, ob = ctx.mode.sig_bytes, ctx.mode.other_bytes
+    for v, nb, what in ((sigma1, n * sb, "sigma'_1"), (sigma2, n * sb, "sigma'_2"), (J, n * ob, "J"),
+                        (T, n * ob, "commitment"), (responses, n * nresp * 48, "responses"),
+                        (chal, n * 48, "challenges"), (revealed_msgs, n * r * 48, "revealed messages")):
+        need(v, nb, what)
+    idx = np.ascontiguousarray(np.asarray(revealed_idx, dtype=np.uint64)) if r else np.zeros(1, np.uint64)
+    verdicts = np.zeros(max(n, 1), dtype=np.uint8)
+    stats = np.zeros(3, dtype=np.uint32)
+    keep = [buf(x) for x in (sigma1, sigma2, J, T, responses, chal, revealed_msgs)]
+    ptrs = [k[0] for k in keep]
+    check(lib.cc_pok_verify_batch_locate(ctx.h, n, q, r, nresp, seg, ptrs[0], ptrs[1], ptrs[2], ptrs[3], ptrs[4],
+                                         ptrs[5], ctypes.c_void_p(idx.ctypes.data), ptrs[6],
+                                         ctypes.c_void_p(verdicts.ctypes.data), ctypes.c_void_p(stats.ctypes.data)),
+          "cc_pok_verify_batch_locate")
+    return verdicts[:n], tuple(int(x) for x in stats)
+
+
 def _fresh_scalars(count: int) -> bytes:
     """count scalars from the OS generator: 48 random bytes each, reduced mod r (bias < 2^-128)."""
     return b"".join((int.from_bytes(secrets.token_bytes(48), "big") % R_ORDER).to_bytes(48, "big")

@@ -47,7 +47,7 @@ static cc_status launch_pok(cc_ctx* c, const VerifyWork& w, size_t n, size_t q, 
 // chip only from 128 proofs a SIMD on (131,072 on 1,024 SIMDs); a batch of half that leaves every
 // second SIMD idle for the whole loop.  While the two-proof loop's waves (64 proofs each) still fit one
 // a SIMD it is the shorter launch: the same twin layout, twice the Miller values for the product tree.
-static bool pok_rlc_twin(cc_ctx* c, size_t n) {
+bool cc::host::pok_rlc_twin(cc_ctx* c, size_t n) {
     if (!c->n_simd) {
         int cu = 0;
         if (hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess || cu <= 0) {

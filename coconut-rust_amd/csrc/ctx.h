@@ -1,6 +1,6 @@
 // Internal header of the C ABI's host side (include/coconut_hip.h), which lives in the capi_*.cpp files, one
 // per area: capi_ctx (contexts, tables, timing, concurrency), capi_verify (Signature::verify, the RLC,
-// device sets), capi_pok, capi_aggregate, capi_issuer, capi_holder, capi_keygen, capi_vss.  Here: the HIP policies of
+// device sets), capi_locate and capi_pok_locate (the RLC locate modes), capi_pok, capi_aggregate, capi_issuer, capi_holder, capi_keygen, capi_vss.  Here: the HIP policies of
 // devbuf.h and slots.h, struct cc_ctx, the stream-ordering helpers, and the helpers more than one area
 // calls.  The cc_* definitions take their C linkage from coconut_hip.h's declarations.  Every compute step
 // runs in the HIP kernels behind launch.h — there is no CPU fallback in this library.
@@ -145,6 +145,7 @@ struct cc_ctx {
     // word per segment, the segmented fold's workspace, the per-partial flags of a finish; the drivers'
     // segment partials and accept bytes, and the compacted rows and verdicts of the rejected segments
     DevBuf seg_any, seg_work, fin_each_flags, loc_parts, loc_accept, loc_s1, loc_s2, loc_msgs, loc_verdicts;
+    DevBuf loc_pok[5];  // the PoK locate driver's compacted J, T, responses, challenges, revealed messages
     // RLC g~-side fold (fold.hip): fold points, delta digits, sort/partials/bucket workspace; the fixed
     // points P_w = (256^w) g~ of the window pairs (SoA, built with the verkey tables) and their
     // identity flags
@@ -332,6 +333,8 @@ static cc_status rlc_host(cc_ctx* c, HostForm& f, size_t n, uint8_t* verdicts, P
     HostForm g(c->stream);
     return each(g);
 }
+// capi_pok.cpp: whether the PoK partial of n proofs takes the two-proof Miller loop (else the four-proof one)
+bool pok_rlc_twin(cc_ctx* c, size_t n);
 // capi_pok.cpp: the PoK forms' checks; capi_aggregate.cpp: the Straus scratch; capi_holder.cpp: the request forms' checks
 cc_status prove_checks(const cc_ctx* c, bool with_vk, size_t q, size_t r, size_t nresp, const uint64_t* rev_idx,
                        std::vector<uint32_t>& idx);

@@ -1,7 +1,7 @@
 // The host launchers of the HIP kernels (cck_*): declared once, for the C ABI sources that call them and
 // for the .hip files that define them.  C linkage admits no overloads, so a definition whose parameters
 // differ from its declaration here does not compile (instead of linking and passing garbage).
-// miller_lz.hip is compiled five ways and defines a different subset each time.
+// miller_lz.hip is compiled six ways and defines a different subset each time.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -89,7 +89,10 @@ int cck_fold_seg(int mode, size_t n, size_t seg, const int8_t* d_dig, const uint
 int cck_fold_window_seg(int mode, size_t n, size_t seg, uint32_t* d_work, uint32_t* d_partials, hipStream_t st);
 int cck_miller4_seg_lz_g2(size_t n, size_t pstride, const uint32_t* d_prep, const uint32_t* d_flags, uint32_t* d_f,
                           size_t fstride, size_t foff, uint32_t* d_qcheck, int qshift, hipStream_t st);
+int cck_miller_twin_seg_lz_g2(size_t n, size_t pstride, const uint32_t* d_prep, const uint32_t* d_flags, uint32_t* d_f,
+                              size_t fstride, size_t foff, uint32_t* d_qcheck, int qshift, hipStream_t st);
 int cck_rlc_seg_flags(size_t n, int segsh, const uint32_t* d_flags, uint32_t* d_any, hipStream_t st);
+int cck_rlc_seg_flags_pok(size_t n, int segsh, const uint32_t* d_flags, uint32_t* d_any, hipStream_t st);
 int cck_rlc_reduce_seg(size_t n, size_t nseg, uint32_t* d_a, uint32_t* d_b, const uint32_t* d_any, uint32_t force,
                        uint32_t* d_partials, hipStream_t st);
 int cck_rlc_gather_each(int mode, size_t k, const uint32_t* d_parts, const uint32_t* d_pw, const uint8_t* d_finf,

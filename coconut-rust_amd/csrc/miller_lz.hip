@@ -190,11 +190,18 @@ static __device__ __noinline__ void t_check(const Tw* T, const uint32_t* prep, s
 // (rlc.hip twin_slot; the second skipped when n is odd); their product goes to element foff + j.
 // qcheck (kTwin, SigG2): each credential's Q (sigma_1) gets the G2 subgroup test from the loop's own T
 // (curve_pl.h miller_t_in_subgroup); a failure sets *qcheck.
+// CC_MILLER_SEG (its own object, Makefile millers_*: the segmented PoK partial's twin loop): qcheck holds one
+// word per segment of 2 << qshift credentials, and the two credentials of loop i share word i >> qshift.
+#ifdef CC_MILLER_SEG
+#define CC_MILLER_TWIN_QSHIFT_PARAM , int qshift
+#else
+#define CC_MILLER_TWIN_QSHIFT_PARAM
+#endif
 template <int SIG, bool kTwin>
 __global__ __launch_bounds__(MB, 2) void k_miller(size_t n, size_t ps, const uint32_t* __restrict__ prep,
                                                const uint32_t* __restrict__ flags, const uint32_t* __restrict__ cst,
                                                uint32_t* __restrict__ fout, size_t fstride, size_t foff,
-                                               uint32_t* __restrict__ qcheck, int pform) {
+                                               uint32_t* __restrict__ qcheck, int pform CC_MILLER_TWIN_QSHIFT_PARAM) {
     constexpr int NP = 2;  // pairs per loop
     __shared__ int32_t lds[2 * TP][MB];
     const size_t i = (blockIdx.x * (size_t)blockDim.x + threadIdx.x) >> 1;  // lane pair: credential (twin: pair)
@@ -270,6 +277,9 @@ __global__ __launch_bounds__(MB, 2) void k_miller(size_t n, size_t ps, const uin
         }
     }
     if (kTwin && kSigG2 && qcheck) {
+#ifdef CC_MILLER_SEG
+        qcheck += i >> qshift;  // the segment's word, outside the loop
+#endif
 #pragma unroll 1
         for (int k = 0; k < NP; k++) {
             if (k ? skip1 : skip0) continue;  // pair-uniform
@@ -401,6 +411,24 @@ extern "C" int CC_MILLER4_LAUNCH(size_t n, size_t pstride, const uint32_t* d_pre
     constexpr int MB = cc::lz::MB;
     hipLaunchKernelGGL((cc::lz::k_miller4<CC_MILLER_SIG>), dim3((unsigned)((2 * m + MB - 1) / MB)), dim3(MB), 0, st, n,
                        pstride, d_prep, d_flags, d_f, fstride, foff, d_qcheck, (int)cc::lz::kAffRp);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+#elif defined(CC_MILLER_SEG)
+// the twin loop (k_miller<2, true>) with one d_qcheck word per segment of 2 << qshift credentials
+// (ceil(n / (2 << qshift)) words): otherwise cck_miller_lz_g2(1, ...), whose constant operand the twin loop
+// does not read.  SigG2 only, as cck_miller4_seg_lz_g2: the segmented PoK partial's SigG1 launch is
+// cck_miller_lz_g1(1, ...) as it is.
+extern "C" int cck_miller_twin_seg_lz_g2(size_t n, size_t pstride, const uint32_t* d_prep, const uint32_t* d_flags,
+                                         uint32_t* d_f, size_t fstride, size_t foff, uint32_t* d_qcheck, int qshift,
+                                         hipStream_t st) {
+    static_assert(CC_MILLER_SIG == 2, "the segmented launch is SigG2's");
+    if (!n) return 0;
+    const size_t m = (n + 1) / 2;
+    if (fstride < foff + m || pstride < m || qshift < 0 || qshift > 62) return -1;
+    constexpr int MB = cc::lz::MB;
+    hipLaunchKernelGGL((cc::lz::k_miller<2, true>), dim3((unsigned)((2 * m + MB - 1) / MB)), dim3(MB), 0, st, n, pstride,
+                       d_prep, d_flags, (const uint32_t*)nullptr, d_f, fstride, foff, d_qcheck, (int)cc::lz::kAffRp,
+                       qshift);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 #else

@@ -267,6 +267,14 @@ __global__ __launch_bounds__(256) void k_rlc_seg_flags(size_t n, int segsh, cons
     const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
     if (i < n && (flags[i] & 35u)) atomicOr(any + (i >> segsh), 1u);
 }
+// the segmented PoK partial (cc_pok_rlc_partial_seg_device), run once after the PoK prep: bits 0, 1, 5 as above
+// and the PoK prep's bits 3 (a failed Schnorr relation) and 6 (J outside the subgroup), for which
+// k_rlc_pok_sigg2 / _sigg1 (pok_rlc.hip) keep raising their single word
+__global__ __launch_bounds__(256) void k_rlc_seg_flags_pok(size_t n, int segsh, const uint32_t* __restrict__ flags,
+                                                           uint32_t* __restrict__ any) {
+    const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (i < n && (flags[i] & (35u | 72u))) atomicOr(any + (i >> segsh), 1u);
+}
 
 // k_rlc_partial_out for the tree level that has nseg elements (SoA stride nseg): block s writes partial
 // s's product and flag words; force: a verkey or g~ outside the subgroup flags every segment
@@ -437,6 +445,13 @@ static void reduce_level(size_t n, const uint32_t* src, uint32_t* dst, hipStream
 int cck_rlc_seg_flags(size_t n, int segsh, const uint32_t* d_flags, uint32_t* d_any, hipStream_t st) {
     if (!n) return 0;
     hipLaunchKernelGGL(k_rlc_seg_flags, dim3(nblocks(n, 256)), dim3(256), 0, st, n, segsh, d_flags, d_any);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// ... of the segmented PoK partial, after cck_prep_pok_rlc (the flag bits of both preps)
+int cck_rlc_seg_flags_pok(size_t n, int segsh, const uint32_t* d_flags, uint32_t* d_any, hipStream_t st) {
+    if (!n) return 0;
+    hipLaunchKernelGGL(k_rlc_seg_flags_pok, dim3(nblocks(n, 256)), dim3(256), 0, st, n, segsh, d_flags, d_any);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

@@ -418,6 +418,65 @@ cc_status cc_pok_verify_batch_rlc(cc_ctx* ctx, size_t n, size_t q, size_t r, siz
                                   const uint8_t* chal, const uint64_t* revealed_idx, const uint8_t* revealed_msgs,
                                   uint8_t* verdicts);
 
+/* PoK RLC locate: the locate mode above for PoKOfSignatureProof::verify.  The batch is checked in segments
+ * of `seg` proofs, each an RLC check of its own (independent deltas: a forged segment passes with
+ * probability <= 2^-127 per segment, and every proof's Schnorr relation is still checked exactly), and only
+ * the segments whose check fails are verified per proof; verdicts always equal cc_pok_verify_batch's.  What
+ * raises segment s's fall-back flag, and nothing outside it: a proof of the segment whose sigma'_1 or
+ * sigma'_2 is the identity or outside the subgroup (SigG2's sigma'_1 test comes from the Miller loop's own T:
+ * two proofs a loop, four past the two-proof limit, and a loop never straddles two segments), whose Schnorr
+ * relation fails, or whose J lies outside the subgroup.  A verkey component or g~ outside the subgroup flags
+ * EVERY segment (the batch is then verified in place).  A proof that fails only the pairing equation raises
+ * no flag: its segment's product is not one.  Shared verkey only; no GT output; these calls take no
+ * concurrency slot (cc_set_concurrency): they wait for the slots' batches and are ordered on the context's
+ * stream, as the signature locate calls are.
+ *   cc_pok_rlc_partial_seg_device : cc_pok_rlc_partial_device in one pass for every segment: S = ceil(n / seg)
+ *                               partials (S x CC_RLC_PARTIAL_WORDS u32, finished by cc_rlc_finish_each_device),
+ *                               partial s covering proofs [s seg, min(n, (s + 1) seg)) and equal to what
+ *                               cc_pok_rlc_partial_device(hi - lo, base_index + s seg, seed32, slice) writes
+ *                               (word for word while both take the same Miller loop: up to 65,536 proofs on
+ *                               an MI355X; beyond, the same decisions).  Errors: those of
+ *                               cc_pok_rlc_partial_device in its order, then seg: a power of two, 4 <= seg <=
+ *                               CC_MAX_BATCH, and S <= CC_MAX_PARTS, else CC_ERR_DECODE.  n = 0: CC_OK, nothing
+ *                               written.
+ *   cc_pok_verify_batch_locate_device : the segmented partial, the per-partial finish, then ONE
+ *                               cc_pok_verify_batch_device launch sequence over the rejected segments only
+ *                               (all seven per-proof arrays compacted device-to-device, a run of adjacent
+ *                               rejected segments at a time; every segment rejected: the batch verified in
+ *                               place); d_verdicts n bytes.  seg = 0: the library's default for the context's
+ *                               group mode (CC_POK_LOCATE_SEG_DEFAULT_G2 / _G1).  SYNCHRONISES `stream` ONCE
+ *                               (the download of the S accept bytes); the recheck is left queued.
+ *                               stats3_or_null: as cc_verify_batch_locate_device (segments, rejected segments,
+ *                               proofs rechecked; HOST words).
+ *   cc_pok_verify_batch_locate : the host form: one upload, a fresh seed from /dev/urandom, the device form,
+ *                               one download.  A device set forwards to its first device, as every PoK host
+ *                               form does.
+ * The defaults come from tools/bench_pok_locate.py on config 5's shape (65,536 proofs, q = 32, 8 revealed,
+ * one MI355X) by the rule of CC_LOCATE_SEG_DEFAULT_*: per mode the segment length with the best
+ * one-bad-proof rate among those whose all-valid rate stays within twice the run's spread of
+ * cc_pok_rlc_partial_device + cc_rlc_finish_device's (SigG2 1,024: 2.0 % below; SigG1 1,024: 1.0 % below).
+ * There one bad proof costs 1.72x less time than the RLC pass plus the per-proof pass in both modes, but the
+ * per-proof path alone is still faster on such a batch (locate reaches 0.92 of its rate in SigG2, 0.85 in
+ * SigG1).  DESIGN.md "PoK RLC locate" has the table. */
+#define CC_POK_LOCATE_SEG_DEFAULT_G2 1024
+#define CC_POK_LOCATE_SEG_DEFAULT_G1 1024
+cc_status cc_pok_rlc_partial_seg_device(cc_ctx* ctx, size_t n, size_t q, size_t r, size_t nresp, size_t seg,
+                                        uint64_t base_index, const uint8_t* seed32, const uint8_t* d_sigma1,
+                                        const uint8_t* d_sigma2, const uint8_t* d_J, const uint8_t* d_T,
+                                        const uint8_t* d_responses, const uint8_t* d_chal,
+                                        const uint64_t* revealed_idx, const uint8_t* d_revealed_msgs,
+                                        uint32_t* d_partials, void* stream);
+cc_status cc_pok_verify_batch_locate_device(cc_ctx* ctx, size_t n, size_t q, size_t r, size_t nresp, size_t seg,
+                                            const uint8_t* seed32, const uint8_t* d_sigma1, const uint8_t* d_sigma2,
+                                            const uint8_t* d_J, const uint8_t* d_T, const uint8_t* d_responses,
+                                            const uint8_t* d_chal, const uint64_t* revealed_idx,
+                                            const uint8_t* d_revealed_msgs, uint8_t* d_verdicts,
+                                            uint32_t* stats3_or_null, void* stream);
+cc_status cc_pok_verify_batch_locate(cc_ctx* ctx, size_t n, size_t q, size_t r, size_t nresp, size_t seg,
+                                     const uint8_t* sigma1, const uint8_t* sigma2, const uint8_t* J, const uint8_t* T,
+                                     const uint8_t* responses, const uint8_t* chal, const uint64_t* revealed_idx,
+                                     const uint8_t* revealed_msgs, uint8_t* verdicts, uint32_t* stats3_or_null);
+
 /* Codec check: decode n encodings of `group` (1 = G1 97 B, 2 = G2 192 B) and
  * report per point 0 = identity (AMCL maps a bad prefix / off-curve point to infinity), 1 = on the
  * curve but outside the order-r subgroup, 2 = in G1 / G2.  The reference never tests membership on

@@ -252,6 +252,41 @@ pub fn pok_verify_batch_pervk(proofs: &[(Vec<u8>, Vec<u8>, Vec<u8>, Vec<u8>, Vec
     v.into_iter().map(|b| b == 1).collect()
 }
 
+/// `pok_verify_batch` through the RLC locate mode (cc_pok_verify_batch_locate): the batch is checked in
+/// segments of `seg` proofs (a power of two >= 4; 0: the engine's default for the group mode), each with its
+/// own random-linear-combination check, and only the rejected segments are verified per proof, so a forged
+/// showing costs its segment's re-verification, not the batch's.  The verdicts equal `pok_verify_batch`'s;
+/// the second value is (segments, rejected segments, proofs rechecked).
+pub fn pok_verify_batch_locate(proofs: &[(Vec<u8>, Vec<u8>, Vec<u8>, Vec<u8>, Vec<FieldElement>)],
+                               chal: &[FieldElement], revealed_idx: &[u64], revealed_msgs: &[Vec<FieldElement>],
+                               vk: &Verkey, params: &Params, seg: usize, ctx: &HipCtx) -> (Vec<bool>, [u32; 3]) {
+    let (n, q, r) = (proofs.len(), vk.Y_tilde.len(), revealed_idx.len());
+    if n == 0 { return (Vec::new(), [0; 3]); }
+    let nresp = proofs[0].4.len();
+    let (sb, ob) = (ctx.sig_bytes(), ctx.oth_bytes());
+    assert_eq!(chal.len(), n, "one challenge per proof");  // len-guard
+    assert!(revealed_msgs.len() == n && revealed_msgs.iter().all(|m| m.len() == r),
+            "r revealed messages per proof");  // len-guard
+    assert!(proofs.iter().all(|p| p.4.len() == nresp), "the same response count for every proof");  // len-guard
+    assert!(proofs.iter().all(|p| p.0.len() == sb && p.1.len() == sb && p.2.len() == ob && p.3.len() == ob),
+            "proof part encodings (sigma'_1, sigma'_2: SignatureGroup; J, T: OtherGroup)");  // len-guard
+    ctx.set_params(&params.g_tilde.to_bytes());
+    ctx.set_verkey(&vk.X_tilde.to_bytes(), &vk.Y_tilde.iter().flat_map(|y| y.to_bytes()).collect::<Vec<u8>>(), q);
+    let cat = |f: &dyn Fn(&(Vec<u8>, Vec<u8>, Vec<u8>, Vec<u8>, Vec<FieldElement>)) -> Vec<u8>| -> Vec<u8> {
+        proofs.iter().flat_map(|p| f(p)).collect()
+    };
+    let (s1, s2, j, t) = (cat(&|p| p.0.clone()), cat(&|p| p.1.clone()), cat(&|p| p.2.clone()), cat(&|p| p.3.clone()));
+    let resp = cat(&|p| p.4.iter().flat_map(|v| v.to_bytes()).collect());
+    let ch: Vec<u8> = chal.iter().flat_map(|c| c.to_bytes()).collect();
+    let rm: Vec<u8> = revealed_msgs.iter().flatten().flat_map(|m| m.to_bytes()).collect();
+    let mut v = vec![0u8; n];
+    let mut stats = [0u32; 3];
+    ctx.check(unsafe { cc_pok_verify_batch_locate(ctx.raw, n, q, r, nresp, seg, s1.as_ptr(), s2.as_ptr(), j.as_ptr(),
+                                                  t.as_ptr(), resp.as_ptr(), ch.as_ptr(), revealed_idx.as_ptr(),
+                                                  rm.as_ptr(), v.as_mut_ptr(), stats.as_mut_ptr()) });
+    (v.into_iter().map(|b| b == 1).collect(), stats)
+}
+
 /// One holder-side proof as its serialized parts: (sigma'_1, sigma'_2, J, T, responses), the tuple
 /// `pok_verify_batch` takes.
 pub type ProofParts = (Vec<u8>, Vec<u8>, Vec<u8>, Vec<u8>, Vec<FieldElement>);

@@ -145,6 +145,24 @@ extern "C" {
                                    sigma1: *const u8, sigma2: *const u8, j: *const u8, t: *const u8,
                                    responses: *const u8, chal: *const u8, revealed_idx: *const u64,
                                    revealed_msgs: *const u8, verdicts: *mut u8) -> c_int;
+    // PoK RLC locate: one partial per segment of `seg` proofs (finished by cc_rlc_finish_each_device), and the
+    // drivers that verify per proof only the rejected segments (stats3: segments, rejected, proofs rechecked)
+    pub fn cc_pok_rlc_partial_seg_device(ctx: *mut CcCtx, n: usize, q: usize, r: usize, nresp: usize, seg: usize,
+                                         base_index: u64, seed32: *const u8, d_sigma1: *const u8,
+                                         d_sigma2: *const u8, d_j: *const u8, d_t: *const u8,
+                                         d_responses: *const u8, d_chal: *const u8, revealed_idx: *const u64,
+                                         d_revealed_msgs: *const u8, d_partials: *mut u32,
+                                         stream: *mut c_void) -> c_int;
+    pub fn cc_pok_verify_batch_locate_device(ctx: *mut CcCtx, n: usize, q: usize, r: usize, nresp: usize, seg: usize,
+                                             seed32: *const u8, d_sigma1: *const u8, d_sigma2: *const u8,
+                                             d_j: *const u8, d_t: *const u8, d_responses: *const u8,
+                                             d_chal: *const u8, revealed_idx: *const u64,
+                                             d_revealed_msgs: *const u8, d_verdicts: *mut u8, stats3: *mut u32,
+                                             stream: *mut c_void) -> c_int;
+    pub fn cc_pok_verify_batch_locate(ctx: *mut CcCtx, n: usize, q: usize, r: usize, nresp: usize, seg: usize,
+                                      sigma1: *const u8, sigma2: *const u8, j: *const u8, t: *const u8,
+                                      responses: *const u8, chal: *const u8, revealed_idx: *const u64,
+                                      revealed_msgs: *const u8, verdicts: *mut u8, stats3: *mut u32) -> c_int;
     // §8(f): codec, hash-to-curve, issuer side, keygen
     pub fn cc_subgroup_check(ctx: *mut CcCtx, group: c_int, n: usize, points: *const u8, status: *mut u8) -> c_int;
     pub fn cc_hash_to_curve(ctx: *mut CcCtx, group: c_int, n: usize, data: *const u8, offsets: *const u64,
