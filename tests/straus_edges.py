@@ -206,13 +206,18 @@ def walk(terms, stop_at=None):
     return None if stop_at is not None else (c, skipped)
 
 
+def butterfly_stage(vals, m, log):
+    """One butterfly stage at distance m: both partners get lower + upper (the lower one is the left operand)."""
+    new = list(vals)
+    for g in range(len(vals)):
+        if not g & m:
+            new[g] = new[g | m] = join(vals[g], vals[g | m], log, M)
+    return new
+
+
 def _butterfly(vals, dists, log):
     for m in dists:
-        new = list(vals)
-        for g in range(len(vals)):
-            if not g & m:
-                new[g] = new[g | m] = join(vals[g], vals[g | m], log, M)
-        vals = new
+        vals = butterfly_stage(vals, m, log)
     return vals[0]
 
 
