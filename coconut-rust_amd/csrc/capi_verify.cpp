@@ -42,6 +42,8 @@ static cc_status launch_miller(cc_ctx* c, const VerifyWork& w, size_t n, hipStre
 cc_status cc::host::launch_pairings(cc_ctx* c, const VerifyWork& w, size_t n, uint8_t* d_verdicts, uint8_t* d_gt,
                                     hipStream_t st) {
     if (c->timing) (void)hipEventRecord(c->ev[1], st);
+    // a g~ that did not decode is the identity: pair 1 is skipped (factor 1), as the reference pairs it
+    if (c->gtilde_inf) KCK(cck_flag_pair1(n, w.flags->as<uint32_t>(), st));
     cc_status ms = launch_miller(c, w, n, st);
     if (ms) return ms;
     if (c->timing) (void)hipEventRecord(c->ev[2], st);

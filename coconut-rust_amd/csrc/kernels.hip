@@ -630,6 +630,22 @@ int cck_gtilde_lines(const uint32_t* d_gtilde_aff, uint32_t* d_lines, hipStream_
     return 0;
 }
 
+// A g~ that decodes to the identity (cc_set_params): pair 1 of every credential is e(., O) = 1, and no prep
+// knows it.  After the prep the n flag words get bit4 (soa.h: pair 1 degenerate), so every Miller kernel
+// skips the pair instead of reading g~'s placeholder coordinates, lazy form or lines.  Launched for such a
+// g~ only (capi_verify.cpp launch_pairings): an honest g~ pays a host branch.
+__global__ __launch_bounds__(256) void k_flag_pair1(size_t n, uint32_t* __restrict__ flags) {
+    const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (i < n) flags[i] |= 16u;
+}
+
+int cck_flag_pair1(size_t n, uint32_t* d_flags, hipStream_t st) {
+    if (!n) return 0;
+    hipLaunchKernelGGL(k_flag_pair1, dim3(nblocks(n, 256)), dim3(256), 0, st, n, d_flags);
+    CC_CHECK(hipGetLastError());
+    return 0;
+}
+
 
 // shared-verkey prep (the fixed-base tables); per-credential verkeys: pervk.hip cck_prep_var
 int cck_prep(int mode, size_t n, int q, const uint8_t* d_s1, const uint8_t* d_s2, const uint8_t* d_msgs,

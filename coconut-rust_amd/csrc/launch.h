@@ -12,6 +12,7 @@ int cck_decode_points(int group, size_t n, const uint8_t* d_bytes, uint32_t* d_o
 int cck_build_table(int group, int nbases, int wbits, const uint32_t* d_bases, const uint32_t* d_inf, uint32_t* d_pw,
                     uint32_t* d_table, int lazy_g2, hipStream_t st);
 int cck_gtilde_lines(const uint32_t* d_gtilde_aff, uint32_t* d_lines, hipStream_t st);
+int cck_flag_pair1(size_t n, uint32_t* d_flags, hipStream_t st);
 int cck_lazy_form(size_t n, const uint32_t* d_in, uint32_t* d_out, hipStream_t st);
 int cck_subgroup(int group, size_t n, const uint8_t* d_bytes, uint8_t* d_status, hipStream_t st);
 int cck_hash_to_curve(int group, size_t n, const uint8_t* d_data, const uint64_t* d_offsets, uint8_t* d_out,

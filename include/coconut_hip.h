@@ -93,7 +93,17 @@ cc_status cc_ctx_num_devices(const cc_ctx* ctx, int* ndev);
 cc_status cc_ctx_destroy(cc_ctx* ctx);
 cc_status cc_ctx_mode(const cc_ctx* ctx, int* mode_out);
 
-/* Params: only g_tilde (OtherGroup encoding) is used on the verify path. */
+/* Params: only g_tilde (OtherGroup encoding) is used on the verify path.  The same g_tilde again is a
+ * no-op.  A new g_tilde under a bound verkey keeps the verkey and rebuilds everything derived from both
+ * (g~'s slot of the verkey block, the fixed-base tables and the RLC window points at the width they had or
+ * the one cc_set_table_bits now asks for, the subgroup status the RLC depends on) before the call
+ * returns, after waiting for the concurrency slots' batches; should that rebuild fail the context is left
+ * WITHOUT a verkey, as after a failed cc_set_verkey.
+ * A g_tilde that does not decode (the identity's encoding, a bad prefix, a point off the curve) is the
+ * identity, as in the reference: every pairing with it is 1, so Signature::verify and the pairing half of
+ * PoKOfSignatureProof::verify reduce to e(sigma_1, pr) = 1, the provers' J and T lose their g~ term, and
+ * the RLC never accepts on its own (its verdicts come from the per-credential path).  Coordinates >= p
+ * are reduced; a point on the curve outside the subgroup is paired as it is. */
 cc_status cc_set_params(cc_ctx* ctx, const uint8_t* g_tilde);
 
 /* Shared verkey (X~, Y~[q]) for cc_verify_batch with vk == NULL: builds fixed-base tables on the
